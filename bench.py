@@ -19,9 +19,11 @@ Multi-GPU: one process per GPU (torch.distributed / RCCL for the barriers, the m
 all_gather at the end of the run); reads are sharded, every rank holds a full index replica; no data-path collective (weak scaling).
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under torch.distributed.run with N ranks.
 
-Output: ONE compact JSON line (< 4 KB) on stdout of rank 0.  Everything else -- the optional legs (host at the 8-GPU thread budget, configs 1 / 4 / 5,
-index-size sweep), per-leg counters, notes -- goes to <workdir>/bench_extra.json (path in the line under "extra"), written by a child process
-so that a fault in an optional leg cannot take the line with it.
+Output: ONE compact JSON line (< 4 KB) on stdout of rank 0.  Everything else -- per-leg counters, notes and, with --extra-legs, the optional legs (host at
+the 8-GPU thread budget, configs 1 / 4 / 5, index-size sweep; ~7 more minutes) -- goes to <workdir>/bench_extra.json (path in the line under "extra"), written
+by a child process so that a fault in an optional leg cannot take the line with it.
+--dump-outputs DIR: after the timed steps, the SAM records of the last step (a fixed, seeded sample of its pairs, rank 0) as DIR/<field>.npy, float64
+(dump_outputs): the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -44,7 +46,7 @@ T_START = time.time()
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (batches of --reads pairs per GPU), >= 1")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--genome-mb", type=int, default=int(os.environ.get("STARAMD_BENCH_GENOME_MB", "3100")))
     ap.add_argument("--reads", type=int, default=int(os.environ.get("STARAMD_BENCH_READS", "400000")), help="read pairs per GPU per step (= --gpuBatchReads)")
@@ -53,20 +55,25 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sweep", action="store_true", help="skip the index-size sweep (100 / 400 / 1000 Mb)")
     ap.add_argument("--no-two-pass", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the optional legs (bench_extra.json): host_budget / config 5 / config 1 / sweep / 2-pass")
+    ap.add_argument("--extra-legs", action="store_true", help="after the line's own work, run the optional legs (bench_extra.json): host_budget / config 5 / config 1 / sweep / 2-pass")
+    ap.add_argument("--no-extra-legs", action="store_true", help="skip the optional legs (the default; overrides --extra-legs)")
     ap.add_argument("--no-exclusive", action="store_true", help="skip the one-context leg the roofline kernel times come from (they are then the overlapped two-context figures)")
     ap.add_argument("--cpu-selftest", action="store_true", help="TEST of this script's plumbing on a box without a GPU: gloo, the oracle behind the front end, a tiny genome; the line says selftest")
     ap.add_argument("--keep-run-dirs", action="store_true", help="do not delete the run directories (FASTQ + SAM) that earlier bench.py runs of other sizes left in the genome cache")
     ap.add_argument("--budget-s", type=float, default=float(os.environ.get("STARAMD_BENCH_BUDGET_S", "1500")), help="optional legs are skipped once this much wall time is used")
     ap.add_argument("--workdir", default=os.environ.get("STARAMD_BENCH_DIR", "/dev/shm/star_amd_bench" if os.path.isdir("/dev/shm") else "/tmp/star_amd_bench"))
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the SAM records of the last timed step as DIR/<field>.npy (dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # data
 
 def genome_dir(args, mb):
-    key = hashlib.md5(("v5g|%d|%d" % (mb, args.read_len)).encode()).hexdigest()[:10]
+    key = hashlib.md5(("v6g|%d|%d" % (mb, args.read_len)).encode()).hexdigest()[:10]          # v6: synth.make_genome_large is reproducible
     return os.path.join(args.workdir, "genome_%dmb_%s" % (mb, key))
 
 
@@ -336,6 +343,65 @@ def full_size_parity(ref, new):
             "log_final_counters_identical": refstar.final_log_counters(ref + "Log.final.out") == refstar.final_log_counters(new + "Log.final.out")}
 
 
+DUMP_SAMPLE_PAIRS = 65536           # pairs of the last step whose records --dump-outputs writes (a fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20261015
+DUMP_FIELDS = ["read_id", "flag", "ref", "pos", "mapq", "cigar_crc32", "mate_ref", "mate_pos", "tlen", "NH", "HI", "AS", "nM"]
+
+
+def dump_outputs(out_dir, sam_path, first_id, n_ids):
+    """--dump-outputs: what the timed path computed in its last step -- the SAM records of the pairs with read ids first_id .. first_id + n_ids - 1 (the FASTQ names
+    them r<id>; the writer emits batches in input order, so they are the tail of the file) -- as one float64 array per field in DIR/<field>.npy, row i of every
+    array = record i.  A fixed, seeded sample of DUMP_SAMPLE_PAIRS of the step's pairs (all of them if fewer); rows sorted by every field, read id first, so that the
+    order in which threads format a batch does not matter; whole reads are dropped from the end if the arrays would exceed DUMP_MAX_BYTES.  Fields: ref / mate_ref =
+    index of the @SQ line (-1: '*'), cigar_crc32 = zlib.crc32 of the CIGAR string, NH / HI / AS / nM = the SAM attributes (-1: absent); pos, mate_pos 1-based as in SAM."""
+    import zlib
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    want = np.zeros(n_ids, dtype=bool)
+    want[rng.choice(n_ids, size=min(n_ids, DUMP_SAMPLE_PAIRS), replace=False)] = True
+    refs = {}
+    with open(sam_path, "rb") as f:
+        for l in f:
+            if not l.startswith(b"@"):
+                break
+            if l.startswith(b"@SQ"):
+                refs[[x for x in l.split(b"\t") if x.startswith(b"SN:")][0][3:].rstrip(b"\n")] = len(refs)
+        size = f.seek(0, 2)
+        span = max(1 << 24, int(1.25 * size * n_ids / (first_id + n_ids)))       # the step's share of the file, and some
+        while True:                      # a tail of the file that begins before the step's first record
+            start = max(0, size - span)
+            f.seek(start)
+            buf = f.read(size - start)
+            if start:
+                buf = buf[buf.index(b"\n") + 1:]
+            lines = [l for l in buf.split(b"\n") if l and not l.startswith(b"@")]
+            if start == 0 or not lines or int(lines[0][1:lines[0].index(b"\t")]) < first_id:
+                break
+            span *= 2
+    rows = []
+    ref_of = lambda s, same: same if s == b"=" else refs.get(s, -1)
+    for l in lines:
+        i = int(l[1:l.index(b"\t")]) - first_id
+        if i < 0 or i >= n_ids or not want[i]:
+            continue
+        t = l.split(b"\t")
+        ref = refs.get(t[2], -1)
+        tags = {x[:2]: x[5:] for x in t[11:]}
+        rows.append([first_id + i, int(t[1]), ref, int(t[3]), int(t[4]), zlib.crc32(t[5]), ref_of(t[6], ref), int(t[7]), int(t[8])] +
+                    [int(tags[k]) if k in tags else -1 for k in (b"NH", b"HI", b"AS", b"nM")])
+    a = np.array(rows, dtype=np.float64).reshape(-1, len(DUMP_FIELDS))
+    a = a[np.lexsort(a.T[::-1])]
+    n = min(len(a), DUMP_MAX_BYTES // (8 * len(DUMP_FIELDS)))
+    if n < len(a):
+        n = int(np.searchsorted(a[:, 0], a[n, 0]))          # whole reads only
+        a = a[:n]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, name in enumerate(DUMP_FIELDS):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[:, k]))
+    return {"dir": out_dir, "records": int(len(a)), "pairs_sampled": int(want.sum()), "first_read_id": first_id, "pairs_in_step": n_ids}
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 
 SELFTEST_CLI_LIB = os.path.join(ROOT, "oracle", "_build", "libstaramd_cli_oracle.so")      # --cpu-selftest only (test of the plumbing, never a measurement)
@@ -550,6 +616,7 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    dumped = dump_outputs(args.dump_outputs, outp + "Aligned.out.sam", n_total - args.reads, args.reads) if args.dump_outputs else None
     steps = max(args.steps, 1)
     lread = 2 * args.read_len + 1
     c, ms, kern, bytes_per_pair = report_dict(rep, lread)
@@ -557,7 +624,7 @@ def main():
     n_ctx = max(1, int(rep.nContexts))
     value = timed_reads_all / elapsed / 1e6
     extra = {"per_kernel_ms_timed_region": ms, "counters_per_pair": {k: (v / n if not isinstance(v, dict) else v) for k, v in c.items() if not k.startswith("_")},
-             "algorithmic_bytes_per_pair_whole_path": bytes_per_pair, "index_build": ginfo, "sj_merge_ms": sj_ms.get("ms"),
+             "algorithmic_bytes_per_pair_whole_path": bytes_per_pair, "index_build": ginfo, "sj_merge_ms": sj_ms.get("ms"), "dump_outputs": dumped,
              "cpu_throttled_in_timed_region": ({"periods": thr1[0] - t_clock["thr0"][0], "ms": (thr1[1] - t_clock["thr0"][1]) / 1e3} if thr1 and t_clock.get("thr0") else None),
              "pipeline": {"timed_wall_s": float(rep.timedWall), "device_s_sum_over_contexts": sum(float(rep.deviceMs[k]) for k in range(n_ctx)) / 1e3,
                           "map_batch_call_s": sum(float(rep.deviceBusy[k]) for k in range(n_ctx)), "engine_contexts_per_gpu": n_ctx // max(1, int(rep.nDevices)),
@@ -651,7 +718,7 @@ def main():
     extra_path = os.path.join(args.workdir, "bench_extra.json")
     extra["notes"] = notes; extra["line"] = line
     json.dump(extra, open(extra_path, "w"))
-    if world == 1 and not args.no_extra_legs:
+    if world == 1 and args.extra_legs and not args.no_extra_legs:
         left = args.budget_s - (time.time() - T_START)
         if left > 60:
             try:

@@ -319,6 +319,12 @@ def make_genome_large(seed, total_mb, n_chr, families=HUMAN_LIKE_FAMILIES, segdu
         cid = torch.repeat_interleave(torch.arange(length.numel(), device=dev), length)
         return tot, cid, torch.arange(tot, device=dev) - start[cid]
 
+    def put(g, dst, val):                    # g[dst] = val where copies overlap as a loop would leave it (the last one wins): index assignment leaves
+        s, order = torch.sort(dst, stable=True)          # the winner among repeated positions to the threads, and the genome would change from run to run
+        last = torch.ones_like(s, dtype=torch.bool)
+        last[:-1] = s[1:] != s[:-1]
+        g[s[last]] = val[order[last]]
+
     for c0, c1 in bounds:
         m = c1 - c0; mbc = m / 1e6
         g = ri(0, 4, m, torch.uint8)
@@ -340,7 +346,7 @@ def make_genome_large(seed, total_mb, n_chr, families=HUMAN_LIKE_FAMILIES, segdu
                 r = rev[cid]
                 base = torch.where(r, 3 - base, base)
                 dst = torch.where(r, pos[cid] + (length[cid] - 1 - off), pos[cid] + off)
-                g[dst] = base
+                put(g, dst, base)
                 covered += tot
         for _ in range(int(segdup_per_mb * mbc) + 1):         # recent segmental duplications (inside the chromosome)
             ln = int(ri(10000, 40000, 1).item())
@@ -358,7 +364,7 @@ def make_genome_large(seed, total_mb, n_chr, families=HUMAN_LIKE_FAMILIES, segdu
                 pos = ri(0, m - 200, kk); ln = ri(15, 60, kk)
                 motif = ri(0, 4, kk * motif_len, torch.uint8).reshape(kk, motif_len)
                 tot, cid, off = flat(ln)
-                g[pos[cid] + off] = motif[cid, off % motif_len]
+                put(g, pos[cid] + off, motif[cid, off % motif_len])
         g = acgt[g.long()]
         kn = int(n_runs_per_mb * mbc)
         if kn and m > 100:

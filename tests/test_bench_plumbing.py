@@ -42,6 +42,35 @@ def test_line_is_compact_and_counts_ranks(gpus, tmp_path):
     assert abs(d["value"] * d["ms_per_step"] * d["steps"] * 1e3 - gpus * 2 * 2000) < 0.05 * gpus * 4000      # (value is rounded to 4 digits: ~1 % at this tiny rate)
 
 
+def test_dump_outputs_are_the_last_step_and_repeat(tmp_path):
+    """--dump-outputs: float arrays of one length, at most 64 MB, only reads of the last timed step, and the same arrays from a second run in a fresh work
+    directory (genome, index and reads generated again from their seeds)"""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    got = []
+    for run in ("a", "b"):
+        out = tmp_path / ("dump_" + run)
+        p = subprocess.run([sys.executable, BENCH, "--cpu-selftest", "--steps", "3", "--warmup", "1", "--workdir", str(tmp_path / ("work_" + run)), "--dump-outputs", str(out)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env)
+        assert p.returncode == 0, p.stderr[-2000:]
+        d, n = _line(p.stdout)
+        assert d["steps"] == 3 and n < 4000
+        files = sorted(os.listdir(out))
+        assert files and all(f.endswith(".npy") for f in files)
+        got.append({f: np.load(os.path.join(out, f)) for f in files})
+    a, b = got
+    assert sorted(a) == sorted(b)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    lens = {len(x) for x in a.values()}
+    assert len(lens) == 1 and lens.pop() > 1000
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64), f
+        assert np.array_equal(a[f], b[f]), f
+    ids = a["read_id.npy"]
+    assert ids.min() >= 3 * 2000 and ids.max() < 4 * 2000           # the self-test maps 2000 pairs per step: ids 6000 .. 7999 are the last of 1 + 3 steps
+    assert (a["pos.npy"] >= 0).all() and (a["ref.npy"] >= -1).all()
+
+
 def test_world_size_must_match_gpus(tmp_path):
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, BENCH, "--cpu-selftest", "--gpus", "2", "--workdir", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, env=env)
