@@ -125,7 +125,9 @@ typedef struct staramd_params {
      *      runs the partner loop of ReadAlign::chimericDetectionOld (ReadAlign_chimericDetectionOld.cpp:50-108: best window against the heads of the other
      *      windows and the other transcripts of its own) and returns what 1 returns plus the partner.  A read with a partner has STARAMD_ST_CHIM_PARTNER set;
      *      then maxScoreMate[0] / [1] = chimScoreBest / chimScoreNext of that loop and unmappedLength = index of the partner (relative to trOffset) |
-     *      chimStr of the partner << 30.  Without the bit the loop found none (chimScoreBest 0).  Cuts the result copy of the chimeric configuration ~15x. */
+     *      chimStr of the partner << 30.  Without the bit the loop found none (chimScoreBest 0).  Cuts the result copy of the chimeric configuration ~15x.
+     *      Without chimeric detection (chimSegmentMinPositive 0, as in the 1st pass of a 2-pass run, or chimSegmentMin 0) there is no partner loop: 2 returns
+     *      exactly what 1 returns. */
     uint32_t resultSelect;
     uint32_t chimSegmentMin, chimSegmentReadGapMax;   /* P.pCh.segmentMin, P.pCh.segmentReadGapMax: read by resultSelect 2 only */
 } staramd_params;
@@ -249,8 +251,11 @@ int  staramd_set_novel_junctions(staramd_ctx *ctx, const uint64_t *start, const 
 #define STARAMD_CAP_CHIM_SELECT 1u
 uint32_t staramd_capabilities(void);
 /* Map one batch: replaces the per-read loop around ReadAlign::mapOneRead.
- * STARAMD_ERR_RESULT_OVERFLOW: r->trCount / r->exCount say what the batch needs; its results stay resident, and the next call with the SAME batch
- * (same arrays, same reads) and larger result arrays copies them out without mapping anything again. */
+ * STARAMD_ERR_RESULT_OVERFLOW: r->trCount / r->exCount say what the batch needs; its results stay resident, and the NEXT call on this context, if it is
+ * staramd_map_batch with the SAME batch (same arrays, same contents: every base of its reads, readOffset, mate1Length, mmMaxTotal) and larger result arrays,
+ * copies them out without mapping anything again.  Any other call on the context in between -- staramd_map_batch of another batch, staramd_map_begin,
+ * staramd_map_resident, staramd_update_index / update_tables / insert_junctions / set_novel_junctions (on the context, or on the owner of a context created
+ * with staramd_create_shared) -- drops them, and the batch is mapped again. */
 int  staramd_map_batch(staramd_ctx *ctx, const staramd_batch *b, staramd_results *r);
 /* Same, but the batch is taken from the copy already resident in HBM from the previous call with
  * identical geometry (bench: inputs resident before the timed region). */

@@ -209,6 +209,17 @@ def engine_lib():
         L.staramd_get_counters.argtypes = [C.c_void_p, u64p, C.c_int]
         if hasattr(L, "staramd_launch_count"):
             L.staramd_launch_count.restype = C.c_uint64; L.staramd_launch_count.argtypes = [C.c_void_p]
+        # include/star_amd_async.h, staramd_create_shared, staramd_update_tables (tests of call sequences: tests/history_run.py)
+        L.staramd_create_shared.restype = C.c_int
+        L.staramd_create_shared.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint32, C.c_uint64]
+        L.staramd_update_tables.restype = C.c_int
+        L.staramd_update_tables.argtypes = [C.c_void_p, C.POINTER(Genome), C.POINTER(Params)]
+        L.staramd_map_begin.restype = C.c_int; L.staramd_map_begin.argtypes = [C.c_void_p, C.POINTER(Batch)]
+        L.staramd_map_wait.restype = C.c_int; L.staramd_map_wait.argtypes = [C.c_void_p]
+        L.staramd_map_end.restype = C.c_int; L.staramd_map_end.argtypes = [C.c_void_p, C.POINTER(Results), C.POINTER(Batch)]
+        L.staramd_prefetch_batch.restype = C.c_int; L.staramd_prefetch_batch.argtypes = [C.c_void_p, C.POINTER(Batch)]
+        L.staramd_prefetch_cancel.restype = C.c_int; L.staramd_prefetch_cancel.argtypes = [C.c_void_p]
+        L.staramd_prefetch_hits.restype = C.c_uint64; L.staramd_prefetch_hits.argtypes = [C.c_void_p]
         _engine = L
     return _engine
 
@@ -295,15 +306,23 @@ class HostRun:
 class Engine:
     """The MI355X engine context (one per GPU)."""
 
-    def __init__(self, genome_p, params_p, device=0, max_reads=65536, max_bases=None):
+    def __init__(self, genome_p, params_p, device=0, max_reads=65536, max_bases=None, share_with=None):
+        """share_with: another Engine whose resident index this context maps against (staramd_create_shared); genome_p / params_p are then not used"""
         L = engine_lib()
         self.L = L
         self.ctx = C.c_void_p()
         self.max_reads = max_reads
         max_bases = max_bases or max_reads * 660
-        rc = L.staramd_create(C.byref(self.ctx), device, genome_p, params_p, max_reads, max_bases)
+        if share_with is not None:
+            rc = L.staramd_create_shared(C.byref(self.ctx), share_with.ctx, max_reads, max_bases)
+        else:
+            rc = L.staramd_create(C.byref(self.ctx), device, genome_p, params_p, max_reads, max_bases)
         if rc != 0:
             raise RuntimeError("staramd_create failed (%d): %s" % (rc, L.staramd_last_error().decode()))
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError("%s failed (%d): %s" % (what, rc, self.L.staramd_last_error().decode()))
 
     def update_index(self, genome_p, params_p):
         rc = self.L.staramd_update_index(self.ctx, genome_p, params_p)
@@ -321,6 +340,37 @@ class Engine:
         rc = self.L.staramd_map_batch(self.ctx, C.byref(batch), C.byref(bufs.res))
         if rc != 0:
             raise RuntimeError("staramd_map_batch failed (%d): %s" % (rc, self.L.staramd_last_error().decode()))
+
+    def map_batch_rc(self, batch, bufs):
+        """staramd_map_batch as it is: the return code (STARAMD_ERR_RESULT_OVERFLOW = -3 included), nothing raised, no pieces"""
+        return self.L.staramd_map_batch(self.ctx, C.byref(batch), C.byref(bufs.res))
+
+    def update_tables(self, genome_p, params_p):
+        self._check(self.L.staramd_update_tables(self.ctx, genome_p, params_p), "staramd_update_tables")
+
+    def map_begin(self, batch):
+        self._check(self.L.staramd_map_begin(self.ctx, C.byref(batch)), "staramd_map_begin")
+
+    def map_wait(self):
+        self._check(self.L.staramd_map_wait(self.ctx), "staramd_map_wait")
+
+    def map_end_rc(self, bufs, next_batch=None):
+        return self.L.staramd_map_end(self.ctx, C.byref(bufs.res), C.byref(next_batch) if next_batch is not None else None)
+
+    def map_end(self, bufs, next_batch=None):
+        self._check(self.map_end_rc(bufs, next_batch), "staramd_map_end")
+
+    def prefetch(self, batch):
+        self._check(self.L.staramd_prefetch_batch(self.ctx, C.byref(batch)), "staramd_prefetch_batch")
+
+    def prefetch_cancel(self):
+        self._check(self.L.staramd_prefetch_cancel(self.ctx), "staramd_prefetch_cancel")
+
+    def prefetch_hits(self):
+        return self.L.staramd_prefetch_hits(self.ctx)
+
+    def launch_count(self):
+        return self.L.staramd_launch_count(self.ctx)
 
     def map_resident(self, bufs):
         rc = self.L.staramd_map_resident(self.ctx, C.byref(bufs.res))

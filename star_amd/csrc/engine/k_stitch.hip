@@ -1405,9 +1405,10 @@ extern "C" __global__ void __launch_bounds__(256) k_stitch_finish(const DevIndex
     else if (P.resultSelect) {
         // staramd_params::resultSelect: return only what multMapSelect can pick (ReadAlign_multMapSelect.cpp:26-44):
         // per window the best-first prefix with maxScore + outFilterMultimapScoreRange >= trBest->maxScore
-        // (resultSelect 2: ... and the partner chimeric detection would choose -- the prefix of its window reaches up to it)
+        // (resultSelect 2: ... and the partner chimeric detection would choose -- the prefix of its window reaches up to it.  Without chimeric detection -- the 1st pass
+        // of a 2-pass run sets chimSegmentMinPositive 0 -- there is no partner, and what is returned is exactly what resultSelect 1 returns: k_stitch_win's chimMode)
         ChimSel cs; cs.have = false; cs.scoreBest = cs.scoreNext = 0; cs.strBest = 0; cs.win = cs.rank = 0;
-        if (P.resultSelect == 2u) {
+        if (P.resultSelect == 2u && P.chimSegmentMinPositive && P.chimSegmentMin > 0) {
             u32 ordB = 0, winB = 0;
             for (u32 iw = 0; iw < rd.nWin; iw++) { if (B.wout[rd.winOffset + iw].nTr == 0) continue; if ((i32)ordB == bestW) { winB = iw; break; } ordB++; }
             cs = chimSelectPartner(P, B, rd, ir, winB);
