@@ -37,6 +37,9 @@ void  sah_set_sjdb_device_fn(int (*fn)(int device, const staramd_sjdb_args *, st
  * (follow with staramd_update_tables instead of staramd_update_index); reading it clears it */
 void  sah_set_sjdb_resident_fn(int (*fn)(void *user, const staramd_sjdb_args *, staramd_sjdb_result *), void *user);
 void  sah_engines_ready(void *h);
+/* --gpuBAMcompression Device: every BAM record block is compressed through fn (staramd_bgzf_compress of include/star_amd_bgzf.h, with the compressor as
+ * `user`); process-wide, NULL uninstalls.  A run with Device and no fn installed fails at its first batch. */
+void  sah_set_bgzf_device_fn(int (*fn)(void *user, int level, uint32_t nSeg, const uint8_t *const *in, const uint64_t *inLen, uint8_t *out, uint64_t outCap, uint64_t *outLen), void *user);
 /* chimeric detection (--chimSegmentMin > 0, --chimMultimapNmax 0, no merging of overlapping mates): the engine runs the partner loop (staramd_params::resultSelect 2)
  * instead of returning every transcript of every window.  Call before the engine contexts are created, when staramd_capabilities() has STARAMD_CAP_CHIM_SELECT;
  * returns 1 when the run's parameters now say so, 0 when they do not qualify. */
@@ -50,6 +53,7 @@ const staramd_genome *sah_genome(void *h);                              /* what 
 const staramd_params *sah_params(void *h);
 uint64_t sah_batch_reads(void *h);                                      /* --gpuBatchReads */
 int   sah_device(void *h);                                              /* --gpuDevice */
+int   sah_bgzf_on_device(void *h);                                      /* 1: --gpuBAMcompression Device */
 int   sah_threads(void *h);                                             /* --runThreadN */
 double sah_genome_load_seconds(void *h);
 /* seconds of the post-map stage so far: out[0] waiting for a free text-buffer set, [1] formatting on threads, [2] serial tail of the batches, [3] the writer thread busy */

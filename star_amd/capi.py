@@ -238,6 +238,18 @@ class HostRun:
         self.L = L
         self.genome = L.sah_genome(self.h)
         self.params = L.sah_params(self.h)
+        self._bgzf = None
+
+    def set_bgzf_device(self, bz):
+        """--gpuBAMcompression Device: BAM records of this run are compressed by `bz` (a BgzfDevice; None uninstalls).  The hook is process-wide
+        (sah_set_bgzf_device_fn); close() uninstalls it."""
+        L = self.L
+        L.sah_set_bgzf_device_fn.restype = None; L.sah_set_bgzf_device_fn.argtypes = [C.c_void_p, C.c_void_p]
+        if bz is None:
+            L.sah_set_bgzf_device_fn(None, None)
+        else:
+            L.sah_set_bgzf_device_fn(C.cast(bz.L.staramd_bgzf_compress, C.c_void_p), bz.z)
+        self._bgzf = bz
 
     def next_batch(self, max_reads):
         b = Batch()
@@ -301,6 +313,8 @@ class HostRun:
         if self.h:
             self.L.sah_destroy(self.h)
             self.h = None
+        if self._bgzf is not None:
+            self.set_bgzf_device(None)
 
 
 class Engine:
@@ -391,6 +405,47 @@ class Engine:
         if self.ctx:
             self.L.staramd_destroy(self.ctx)
             self.ctx = C.c_void_p()
+
+
+class BgzfDevice:
+    """include/star_amd_bgzf.h: BGZF compression on the MI355X (k_bgzf.hip in libstaramd.so); lib_path: another library with that ABI (the wave
+    emulator's build of k_bgzf.hip in the CPU tests)."""
+
+    def __init__(self, device=0, initial_bytes=0, lib_path=None):
+        L = C.CDLL(lib_path or _need(ENGINE_PATH))
+        L.staramd_bgzf_create.restype = C.c_int
+        L.staramd_bgzf_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_uint64]
+        L.staramd_bgzf_bound.restype = C.c_uint64; L.staramd_bgzf_bound.argtypes = [C.c_uint64]
+        L.staramd_bgzf_compress.restype = C.c_int
+        L.staramd_bgzf_compress.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_void_p), u64p, C.c_void_p, C.c_uint64, u64p]
+        L.staramd_bgzf_destroy.restype = None; L.staramd_bgzf_destroy.argtypes = [C.c_void_p]
+        L.staramd_bgzf_last_error.restype = C.c_char_p
+        self.L = L
+        self.z = C.c_void_p()
+        if L.staramd_bgzf_create(C.byref(self.z), device, initial_bytes) != 0:
+            raise RuntimeError("staramd_bgzf_create failed: %s" % L.staramd_bgzf_last_error().decode())
+
+    def compress(self, level, segments):
+        """segments: list of bytes -> list of their BGZF members (bytes), one entry per segment"""
+        n = len(segments)
+        keep = [C.create_string_buffer(bytes(s), len(s)) for s in segments]
+        ins = (C.c_void_p * max(n, 1))(*[C.cast(k, C.c_void_p) for k in keep])
+        lens = (C.c_uint64 * max(n, 1))(*[len(s) for s in segments])
+        cap = sum(self.L.staramd_bgzf_bound(len(s)) for s in segments)
+        out = C.create_string_buffer(max(cap, 1))
+        out_len = (C.c_uint64 * max(n, 1))()
+        if self.L.staramd_bgzf_compress(self.z, level, n, ins, lens, out, cap, out_len) != 0:
+            raise RuntimeError("staramd_bgzf_compress failed: %s" % self.L.staramd_bgzf_last_error().decode())
+        raw, res, o = out.raw, [], 0
+        for i in range(n):
+            res.append(raw[o:o + out_len[i]])
+            o += out_len[i]
+        return res
+
+    def close(self):
+        if self.z:
+            self.L.staramd_bgzf_destroy(self.z)
+            self.z = C.c_void_p()
 
 
 class device_sjdb_insertion:

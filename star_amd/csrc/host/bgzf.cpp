@@ -4,6 +4,9 @@
 #include "host.h"
 #include <zlib.h>
 #include <cstring>
+#include <algorithm>
+#include <memory>
+#include <thread>
 
 namespace staramd {
 
@@ -41,6 +44,44 @@ bool bgzfCompress(const std::string &raw, int level, std::string &out) {
         }
     }
     return true;
+}
+
+// ---- --gpuBAMcompression Device: the same members cut on the MI355X (include/star_amd_bgzf.h), through a hook the driver installs
+static BgzfDeviceFn g_bgzfFn = nullptr;
+static void *g_bgzfUser = nullptr;
+const char *const BGZF_DEVICE_MISSING = "EXITING because of fatal PARAMETERS error: --gpuBAMcompression Device, but no device BGZF compressor is installed (sah_set_bgzf_device_fn)";
+void setBgzfDeviceFn(BgzfDeviceFn fn, void *user) { g_bgzfFn = fn; g_bgzfUser = user; }
+bool bgzfDeviceInstalled() { return g_bgzfFn != nullptr; }
+
+std::string bgzfCompressDevice(const std::vector<BgzfJob> &jobs, int threads) {
+    if (!g_bgzfFn) return BGZF_DEVICE_MISSING;
+    std::vector<int> levels;
+    for (const BgzfJob &j : jobs) if (std::find(levels.begin(), levels.end(), j.level) == levels.end()) levels.push_back(j.level);
+    for (int level : levels) {
+        std::vector<const uint8_t *> in; std::vector<uint64_t> len; std::vector<std::string *> outs;
+        uint64_t cap = 0;
+        for (const BgzfJob &j : jobs) {
+            if (j.level != level || j.in->empty()) continue;
+            in.push_back((const uint8_t *)j.in->data()); len.push_back(j.in->size()); outs.push_back(j.out);
+            cap += j.in->size() + 31 * ((j.in->size() + BGZF_INPUT_MAX - 1) / BGZF_INPUT_MAX);     // staramd_bgzf_bound
+        }
+        if (in.empty()) continue;
+        // one output buffer per thread, kept between batches (uninitialised: only what the device returns is touched)
+        static thread_local std::unique_ptr<uint8_t[]> buf; static thread_local uint64_t bufCap = 0;
+        if (bufCap < cap) { bufCap = cap + cap / 4; buf.reset(new uint8_t[bufCap]); }
+        std::vector<uint64_t> outLen(in.size()), at(in.size() + 1, 0);
+        if (g_bgzfFn(g_bgzfUser, level, (uint32_t)in.size(), in.data(), len.data(), buf.get(), cap, outLen.data()) != 0) return "EXITING because of fatal ERROR: BGZF compression failed";
+        for (size_t i = 0; i < in.size(); i++) at[i + 1] = at[i] + outLen[i];
+        std::atomic<size_t> next(0);
+        const char *base = (const char *)buf.get();          // (the helper threads have thread_local buffers of their own)
+        auto put = [&] { for (size_t i; (i = next.fetch_add(1)) < outs.size();) outs[i]->append(base + at[i], outLen[i]); };
+        std::vector<std::thread> th;
+        const size_t W = std::min<size_t>(outs.size(), (size_t)std::max(1, std::min(threads, 8)));
+        for (size_t w = 1; w < W; w++) th.emplace_back(put);
+        put();
+        for (auto &t : th) t.join();
+    }
+    return "";
 }
 
 // the 28-byte end-of-file marker block

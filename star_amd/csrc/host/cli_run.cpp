@@ -35,6 +35,16 @@
 #include "../../../include/star_amd_index.h"
 #include "../../../include/star_amd_cli.h"
 #include "../../../include/star_amd_async.h"
+#include "../../../include/star_amd_bgzf.h"
+
+// the device BGZF compressor (k_bgzf.hip) is in the shipped engine library only: the front ends linked against the oracle / the emulated engine run
+// without it, and a run that asks for it there fails at its first batch (sah_set_bgzf_device_fn)
+extern "C" {
+__attribute__((weak)) int staramd_bgzf_create(staramd_bgzf **out, int device, uint64_t initialInputBytes);
+__attribute__((weak)) int staramd_bgzf_compress(void *z, int level, uint32_t nSeg, const uint8_t *const *in, const uint64_t *inLen, uint8_t *out, uint64_t outCap, uint64_t *outLen);
+__attribute__((weak)) void staramd_bgzf_destroy(staramd_bgzf *z);
+__attribute__((weak)) const char *staramd_bgzf_last_error(void);
+}
 
 namespace {
 typedef std::chrono::steady_clock Clock;
@@ -215,6 +225,16 @@ int staramd_cli_main(int argc, char **argv, const staramd_cli_hooks *hooks, star
             sah_destroy(h); return 105;
         }
         rep.indexUploadSeconds = since(tu);
+    }
+    // --gpuBAMcompression Device: one compressor on the first device, installed as the host library's hook for the length of the run
+    struct BgzfOwner { staramd_bgzf *z = nullptr; ~BgzfOwner() { if (z) { sah_set_bgzf_device_fn(nullptr, nullptr); staramd_bgzf_destroy(z); } } } bgzf;
+    if (sah_bgzf_on_device(h) && staramd_bgzf_create && staramd_bgzf_compress && staramd_bgzf_destroy && staramd_bgzf_last_error) {
+        if (staramd_bgzf_create(&bgzf.z, devices[0], 0)) {
+            fprintf(stderr, "\nEXITING because of FATAL ERROR: cannot initialise the BGZF compressor on device %d: %s\n", devices[0], staramd_bgzf_last_error());
+            destroyAll();
+            sah_destroy(h); return 105;
+        }
+        sah_set_bgzf_device_fn(staramd_bgzf_compress, bgzf.z);
     }
 #ifndef STARAMD_NO_RESIDENT_SJDB
     // junction insertion between the passes runs on the arrays resident in HBM, on every context (no host copy of the new SA unless it is to be saved)

@@ -93,6 +93,7 @@ struct RunParams {
     bool outSAMprimaryAllBest = false;
     bool outSAMmodeNoQS = false;
     bool outBAMunsorted = false, outBAMcoord = false; bool outSAMnone = false; int outBAMcompression = 1;   // --outSAMtype BAM Unsorted | None, --outBAMcompression
+    bool gpuBAMdevice = false;           // --gpuBAMcompression Device: BAM records deflated on the MI355X through the hook of setBgzfDeviceFn
     std::vector<std::string> outSAMattrOrder = {"NH", "HI", "AS", "nM"};   // Standard
     bool attrNMorMD = false, attrHasCh = false;
     std::vector<std::string> outSAMattrOrderQuant;   // attributes of Aligned.toTranscriptome.out.bam: NH HI, then RG / MC if requested (Parameters_samAttributes.cpp:43-47,96-111)
@@ -368,6 +369,14 @@ struct QuantPatch { uint32_t ir; uint32_t nAlignT; std::vector<uint64_t> recOffs
 // ---- BGZF framing of BAM output (bgzf.cpp) ----
 bool bgzfCompress(const std::string &raw, int level, std::string &out);
 void bgzfEof(std::string &out);
+// --gpuBAMcompression Device: the compressor of include/star_amd_bgzf.h (staramd_bgzf_compress), installed by the driver (sah_set_bgzf_device_fn)
+typedef int (*BgzfDeviceFn)(void *user, int level, uint32_t nSeg, const uint8_t *const *in, const uint64_t *inLen, uint8_t *out, uint64_t outCap, uint64_t *outLen);
+void setBgzfDeviceFn(BgzfDeviceFn fn, void *user);
+bool bgzfDeviceInstalled();
+// one hook call per level: job i's input compressed and APPENDED to *out[i] (same members as bgzfCompress would cut); "" or the error text
+struct BgzfJob { const std::string *in; std::string *out; int level; };
+std::string bgzfCompressDevice(const std::vector<BgzfJob> &jobs, int threads);
+extern const char *const BGZF_DEVICE_MISSING;
 
 // sort key of one BAM record (BAMoutput::coordOneAlign, BAMbinSortByCoordinate.cpp:45-56): (refID << 32 | pos, read order, order of production)
 struct BamKey { uint64_t g, r; uint64_t off; uint32_t len; uint32_t chunk; };

@@ -280,6 +280,7 @@ std::string RunParams::parse(int argc, char **argv) {
         else if (k == "outFilterScoreMinOverLread") outFilterScoreMinOverLread = D(k, v);
         else if (k == "outFilterMatchNmin") { outFilterMatchNmin = (uint32_t)U(k, v); dev.outFilterMatchNmin = outFilterMatchNmin; }
         else if (k == "outFilterMatchNminOverLread") outFilterMatchNminOverLread = D(k, v);
+        else if (k == "gpuBAMcompression") { const std::string &s = one(k, v); if (s == "Device") gpuBAMdevice = true; else if (s == "Host") gpuBAMdevice = false; else err = "EXITING: --gpuBAMcompression takes Host or Device"; }
         else if (k == "gpuResultSelect") { const std::string &s = one(k, v); if (s == "All") dev.resultSelect = 0; else if (s == "Selected") dev.resultSelect = 1; else err = "EXITING: --gpuResultSelect takes All or Selected"; }
         else if (k == "outFilterIntronMotifs") { const std::string &s = one(k, v); if (s == "None") dev.outFilterIntronMotifs = 0; else if (s == "RemoveNoncanonical") dev.outFilterIntronMotifs = 1; else if (s == "RemoveNoncanonicalUnannotated") dev.outFilterIntronMotifs = 2; else err = "EXITING because of FATAL INPUT error: unrecognized value of --outFilterIntronMotifs=" + s; }
         else if (k == "outFilterIntronStrands") { const std::string &s = one(k, v); if (s == "RemoveInconsistentStrands") dev.outFilterIntronStrandsRemoveInconsistent = 1; else if (s == "None") dev.outFilterIntronStrandsRemoveInconsistent = 0; else err = "EXITING: unsupported --outFilterIntronStrands " + s; }

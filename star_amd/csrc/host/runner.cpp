@@ -305,6 +305,9 @@ struct Runner {
         if (P.wasp && !pass1 && !wasp) { error = "EXITING because of FATAL ERROR: --waspOutputMode: the allele-swapped reads of the batch were not mapped (sah_wasp_batch / sah_wasp_results)"; return false; }
         const std::vector<int8_t> *waspType = (wasp && !pass1) ? &wasp->type : nullptr;
         if (mg && (mg->reads.n == 0 || !mgRes)) { if (mg->reads.n > 0) { error = "EXITING because of FATAL ERROR: --peOverlapNbasesMin: the merged mates of the batch were not mapped (sah_merged_batch / sah_emit_merged)"; return false; } mg = nullptr; }
+        // --gpuBAMcompression Device: the ranges leave their BAM records uncompressed, one hook call per level compresses them after the join
+        const bool devBam = P.gpuBAMdevice && ((((P.outBAMunsorted || P.outBAMcoord) && !post->samOff)) || (P.quantTrSAM && quantOut && !pass1));
+        if (devBam && !bgzfDeviceInstalled()) { error = BGZF_DEVICE_MISSING; return false; }
         // T contiguous read ranges, each with buffers of its own, formatted by Wk worker threads that take the next range when they are done with one: with as many
         // ranges as threads the section lasts as long as its slowest thread, and on a shared host (the GPU boxes: 16 CPUs of a 256-thread machine) one descheduled
         // thread held the batch for several times the mean (per-thread busy 2.5 - 5.6 ms in a 24 ms section).  Four ranges per thread; gene counting keeps one
@@ -332,6 +335,7 @@ struct Runner {
         std::vector<std::vector<BamKey> > keyss(P.outBAMcoord ? T : 0);
         const bool trSAM = P.quantTrSAM && quantOut && !pass1;       // twoPassRunPass1.cpp:24-29
         std::vector<std::string> qraws(trSAM ? T : 0); std::vector<std::vector<QuantPatch> > qpatches(trSAM ? T : 0);
+        std::vector<std::string> onlys(devBam ? T : 0), qzs(devBam && trSAM ? T : 0); std::vector<char> cuts(devBam ? T : 0, 0);
         const bool chimOn = P.chim.segmentMin > 0 && !pass1;        // twoPassRunPass1.cpp:24: no chimeric detection in the 1st pass
         std::vector<std::string> chims(chimOn ? T : 0), chimSams(chimOn && chimSamOut ? T : 0);
         const bool unm = P.outReadsUnmappedFastx && !pass1;
@@ -403,9 +407,11 @@ struct Runner {
                 std::string only; size_t pos = 0;
                 for (BamKey &k : keyss[t]) if (k.len & 0x80000000u) { k.len &= 0x7fffffffu; only.append(raw, pos, k.off - pos); pos = k.off + k.len; }
                 only.append(raw, pos, std::string::npos);
+                if (devBam) { onlys[t].swap(only); cuts[t] = 1; return; }
                 if (errs[t].empty() && !bgzfCompress(only, P.outBAMcompression, samL)) errs[t] = "EXITING because of fatal ERROR: BGZF compression failed";
                 return;
             }
+            if (devBam) return;
             if (errs[t].empty() && P.outBAMunsorted && !bgzfCompress(raw, P.outBAMcompression, samL)) errs[t] = "EXITING because of fatal ERROR: BGZF compression failed";
         };
         if (T == 1) work(0);
@@ -422,6 +428,29 @@ struct Runner {
             fprintf(stderr, "  emit: %u ranges on %u threads, section %.2f ms, per-range min %.2f / mean %.2f / max %.2f ms\n", T, std::min(Wk, T), std::chrono::duration<double, std::milli>(te2 - te1).count(), mn, sm / T, mx); }
         struct AddTail { double &acc; std::chrono::steady_clock::time_point t0; ~AddTail() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } addTail{tEmitTail, te2};
         for (uint32_t t = 0; t < T; t++) if (!errs[t].empty() && error.empty()) error = errs[t];
+        // one random number per mapped read, in read order, picks the primary transcriptomic alignment (ReadAlign_quantTranscriptome.cpp:69);
+        // the flag is patched into the records (FLAG is the high half of the 5th word) before they are compressed
+        auto patchQuant = [&](uint32_t t) {
+            for (const QuantPatch &qp : qpatches[t]) {
+                uint32_t pick = randomOrder ? multOrder.quantPick[qp.ir] : (uint32_t)(int)(rngUniformReal0to1(rngMultOrder) * qp.nAlignT);
+                for (size_t k = 0; k < qp.recOffset.size(); k++) {
+                    uint8_t &hi = (uint8_t &)qraws[t][qp.recOffset[k] + 19];
+                    if (qp.recAlign[k] == pick) hi &= (uint8_t)~1u; else hi |= 1u;
+                }
+            }
+        };
+        if (devBam && error.empty()) {
+            const auto td0 = std::chrono::steady_clock::now();
+            std::vector<BgzfJob> jobs;
+            if ((P.outBAMunsorted || P.outBAMcoord) && !post->samOff)
+                for (uint32_t t = 0; t < T; t++) {
+                    if (cuts[t]) jobs.push_back({&onlys[t], &o.sams[t], P.outBAMcompression});
+                    else if (P.outBAMunsorted) jobs.push_back({&o.raws[t], &o.sams[t], P.outBAMcompression});
+                }
+            if (trSAM) for (uint32_t t = 0; t < T; t++) { patchQuant(t); jobs.push_back({&qraws[t], &qzs[t], P.quantTrBAMcompression}); }
+            error = bgzfCompressDevice(jobs, P.runThreadN);
+            if (hostTiming) fprintf(stderr, "  emit: BAM records of %zu ranges compressed on the device, %.2f ms\n", jobs.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count());
+        }
         if (!error.empty()) o.used = 0;
         { std::lock_guard<std::mutex> l(wm); fullSets.push_back(k); }
         wcv.notify_all();
@@ -429,18 +458,11 @@ struct Runner {
         for (uint32_t t = 0; t < T; t++) { sj.mergeFrom(sjs[t]); stats.add(sts[t]); if (quant) geneCounts.add(gcs[t]); }
         if (hostTiming) fprintf(stderr, "  emit tail: junction records merged %.2f ms (%zu in the table)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te2).count(), sj.data.size());
         if (trSAM) {
-            // one random number per mapped read, in read order, picks the primary transcriptomic alignment (ReadAlign_quantTranscriptome.cpp:69);
-            // the flag is patched into the records (FLAG is the high half of the 5th word), then the text is compressed and written
             for (uint32_t t = 0; t < T; t++) {
-                for (const QuantPatch &qp : qpatches[t]) {
-                    uint32_t pick = randomOrder ? multOrder.quantPick[qp.ir] : (uint32_t)(int)(rngUniformReal0to1(rngMultOrder) * qp.nAlignT);
-                    for (size_t k = 0; k < qp.recOffset.size(); k++) {
-                        uint8_t &hi = (uint8_t &)qraws[t][qp.recOffset[k] + 19];
-                        if (qp.recAlign[k] == pick) hi &= (uint8_t)~1u; else hi |= 1u;
-                    }
-                }
                 std::string z;
-                if (!bgzfCompress(qraws[t], P.quantTrBAMcompression, z) || fwrite(z.data(), 1, z.size(), quantOut) != z.size()) { error = "EXITING because of fatal ERROR: could not write Aligned.toTranscriptome.out.bam"; return false; }
+                if (!devBam) patchQuant(t);                          // (Device: patched and compressed before the hand-over above)
+                const std::string &zt = devBam ? qzs[t] : z;
+                if ((!devBam && !bgzfCompress(qraws[t], P.quantTrBAMcompression, z)) || fwrite(zt.data(), 1, zt.size(), quantOut) != zt.size()) { error = "EXITING because of fatal ERROR: could not write Aligned.toTranscriptome.out.bam"; return false; }
             }
         }
         if (chimOn && chimOut) for (uint32_t t = 0; t < T; t++) if (!chims[t].empty()) fwrite(chims[t].data(), 1, chims[t].size(), chimOut);
@@ -494,17 +516,27 @@ struct Runner {
         const uint64_t T = (uint64_t)std::max(1, std::min(P.runThreadN, 64));
         const uint64_t per = std::max<uint64_t>(4096, (n + 4 * T - 1) / (4 * T));          // records per slice; slices are written in order
         bool failed = false;
+        const bool dev = P.gpuBAMdevice;                          // --gpuBAMcompression Device: the slices of one round in one hook call
+        if (dev && n > 0 && !bgzfDeviceInstalled()) { if (!toStdout) fclose(f); return BGZF_DEVICE_MISSING; }
+        std::string devErr;
         for (uint64_t base = 0; base < n && !failed; base += per * T) {
-            std::vector<std::string> outS(T); std::vector<std::thread> th;
+            std::vector<std::string> outS(T), raws(dev ? T : 0); std::vector<std::thread> th;
             auto work = [&](uint64_t t) {
                 uint64_t lo = std::min(n, base + t * per), hi = std::min(n, lo + per);
                 std::string raw;
                 for (uint64_t i = lo; i < hi; i++) { const BamKey &k = K[ord[i]]; raw.append(coordChunks[k.chunk], k.off, k.len); }
-                if (!bgzfCompress(raw, P.outBAMcompression, outS[t])) failed = true;
+                if (dev) raws[t].swap(raw);
+                else if (!bgzfCompress(raw, P.outBAMcompression, outS[t])) failed = true;
             };
             for (uint64_t t = 1; t < T; t++) th.emplace_back(work, t);
             work(0);
             for (auto &x : th) x.join();
+            if (dev) {
+                std::vector<BgzfJob> jobs;
+                for (uint64_t t = 0; t < T; t++) jobs.push_back({&raws[t], &outS[t], P.outBAMcompression});
+                devErr = bgzfCompressDevice(jobs, P.runThreadN);
+                if (!devErr.empty()) { failed = true; break; }
+            }
             for (uint64_t t = 0; t < T; t++) if (!outS[t].empty() && fwrite(outS[t].data(), 1, outS[t].size(), f) != outS[t].size()) failed = true;
         }
         std::string e; bgzfEof(e); fwrite(e.data(), 1, e.size(), f);
@@ -516,6 +548,7 @@ struct Runner {
             if (!werr.empty()) return werr;
         }
         coordChunks.clear(); coordKeys.clear();
+        if (!devErr.empty()) return devErr;
         return failed ? "EXITING because of fatal ERROR: could not write " + path : "";
     }
     bool emit(const staramd_results *r, const staramd_results *rMerged = nullptr) { return emitBatch(batch, r, P.peOverlapNbasesMin > 0 && P.dev.readNmates == 2 ? &mergedMain : nullptr, rMerged, P.wasp ? &waspMain : nullptr); }
@@ -624,6 +657,7 @@ uint64_t sah_batch_reads(void *h) { return ((Runner *)h)->P.gpuBatchReads; }
 // junction insertion (2-pass, --sjdbGTFfile / --sjdbFileChrStartEnd at the mapping stage, genomeGenerate with annotations) on the device:
 // fn = staramd_sjdb_insert of the engine library (include/star_amd_index.h); process-wide; NULL restores the host restatement
 void sah_set_sjdb_device_fn(int (*fn)(int, const staramd_sjdb_args *, staramd_sjdb_result *), int device) { staramd::setSjdbDeviceFn(fn, device); }
+void sah_set_bgzf_device_fn(staramd::BgzfDeviceFn fn, void *user) { staramd::setBgzfDeviceFn(fn, user); }
 // the same on the arrays resident in the engine contexts (staramd_insert_junctions for every context): fn(user, args, result); the front end calls
 // sah_engines_ready once its contexts hold the index, and asks sah_index_in_engine after a phase change whether a re-upload is needed at all
 void sah_set_sjdb_resident_fn(int (*fn)(void *, const staramd_sjdb_args *, staramd_sjdb_result *), void *user) { staramd::setSjdbResidentFn(fn, user); }
@@ -662,6 +696,7 @@ int sah_generate_finish(void *h, uint64_t nSA, uint64_t nSAbyte, uint64_t nSAiby
 }
 int sah_tool_done(void *h) { return ((Runner *)h)->toolDone ? 1 : 0; }     // 1: the run was a tool mode (--runMode inputAlignmentsFromBAM) and is finished
 int sah_device(void *h) { return ((Runner *)h)->P.gpuDevice; }
+int sah_bgzf_on_device(void *h) { return ((Runner *)h)->P.gpuBAMdevice ? 1 : 0; }
 double sah_genome_load_seconds(void *h) { return ((Runner *)h)->gi.loadSeconds; }
 void sah_cpu_add(int stage, uint64_t ns) { staramd::cpuAdd(stage, ns); }
 void sah_cpu_seconds(double out[8], int reset) { for (int i = 0; i < staramd::CPU_NSTAGE; i++) out[i] = (double)staramd::cpuTake(i, reset != 0) * 1e-9; }
