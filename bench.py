@@ -13,13 +13,19 @@ Contract (see the task statement): `python bench.py --gpus N --steps K --warmup 
               the index is generated INSIDE the run on the GPU (star_amd --runMode genomeGenerate: the reference needs ~20 min for it)
   roofline  = dominant kernel by HIP-event time on the engine's stream, summed over the timed batches: algorithmic bytes / duration
               vs the 8 TB/s HBM peak
-  cpu_baseline = the reference itself (oracle/_ref/STAR) on the same FASTQ and the same index, --runThreadN = all host cores, with an
+  cpu_baseline = (--full) the reference itself (oracle/_ref/STAR) on the same FASTQ and the same index, --runThreadN = all host cores, with an
               input chunk small enough that every thread has work (>= 8 chunks per thread)
+A plain run does what the line's headline needs and nothing else: the data, the warm-up and timed steps, --dump-outputs, the line.  The data (genome,
+index, reads; seeded, the same bytes in every run) are generated when --workdir does not hold them for this size and kept there, as before --full existed:
+generating them takes 50 - 60 s on one MI355X, 33 - 43 s of it the product's own genomeGenerate of the 3.1 Gb index, so only a run that finds them spends
+less than 30 s outside its steps (15 - 20 s, ~10 s of it index load + upload).  data_prep_s in the line says which case a run was.
+--full adds, after the timed run, what takes runs of its own: cpu_baseline, full_size_parity (the reference's outputs against the run's), the one-context
+leg of the kernel times (kernel_ms_exclusive: only with more than one engine context per GPU, not the default) and, with --extra-legs, the optional legs.
 Multi-GPU: one process per GPU (torch.distributed / RCCL for the barriers, the max-over-ranks reduction and the junction-table
 all_gather at the end of the run); reads are sharded, every rank holds a full index replica; no data-path collective (weak scaling).
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-executes itself under torch.distributed.run with N ranks.
 
-Output: ONE compact JSON line (< 4 KB) on stdout of rank 0.  Everything else -- per-leg counters, notes and, with --extra-legs, the optional legs (host at
+Output: ONE compact JSON line (< 4 KB) on stdout of rank 0.  Everything else -- per-leg counters, notes and, with --full --extra-legs, the optional legs (host at
 the 8-GPU thread budget, configs 1 / 4 / 5, index-size sweep; ~7 more minutes) -- goes to <workdir>/bench_extra.json (path in the line under "extra"), written
 by a child process so that a fault in an optional leg cannot take the line with it.
 --dump-outputs DIR: after the timed steps, the SAM records of the last step (a fixed, seeded sample of its pairs, rank 0) as DIR/<field>.npy, float64
@@ -52,12 +58,14 @@ def parse():
     ap.add_argument("--reads", type=int, default=int(os.environ.get("STARAMD_BENCH_READS", "400000")), help="read pairs per GPU per step (= --gpuBatchReads)")
     ap.add_argument("--read-len", type=int, default=101)
     ap.add_argument("--host-threads", type=int, default=int(os.environ.get("STARAMD_BENCH_HOST_THREADS", "0")), help="post-map threads per rank (0: min(64, cores/ranks))")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed run, also measure and check what the headline does not need: the reference on the same input "
+                                                         "(cpu_baseline), full-size parity against it, the one-context kernel-time leg; with --extra-legs, the optional legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the reference run and the full-size parity")
     ap.add_argument("--no-sweep", action="store_true", help="skip the index-size sweep (100 / 400 / 1000 Mb)")
     ap.add_argument("--no-two-pass", action="store_true")
-    ap.add_argument("--extra-legs", action="store_true", help="after the line's own work, run the optional legs (bench_extra.json): host_budget / config 5 / config 1 / sweep / 2-pass")
+    ap.add_argument("--extra-legs", action="store_true", help="with --full: after the line's own work, run the optional legs (bench_extra.json): host_budget / config 5 / config 1 / sweep / 2-pass")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip the optional legs (the default; overrides --extra-legs)")
-    ap.add_argument("--no-exclusive", action="store_true", help="skip the one-context leg the roofline kernel times come from (they are then the overlapped two-context figures)")
+    ap.add_argument("--no-exclusive", action="store_true", help="--full without the one-context leg the roofline kernel times come from (they are then the overlapped two-context figures)")
     ap.add_argument("--cpu-selftest", action="store_true", help="TEST of this script's plumbing on a box without a GPU: gloo, the oracle behind the front end, a tiny genome; the line says selftest")
     ap.add_argument("--keep-run-dirs", action="store_true", help="do not delete the run directories (FASTQ + SAM) that earlier bench.py runs of other sizes left in the genome cache")
     ap.add_argument("--budget-s", type=float, default=float(os.environ.get("STARAMD_BENCH_BUDGET_S", "1500")), help="optional legs are skipped once this much wall time is used")
@@ -66,6 +74,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.extra_legs and not args.no_extra_legs and not args.full:
+        ap.error("--extra-legs runs after the checks of --full: pass both")
     return args
 
 
@@ -526,9 +536,10 @@ def main():
     if not os.path.isfile(cli_lib):
         raise RuntimeError(cli_lib + " is missing (python -c 'import __graft_entry__ as g; g.build()')")
     if selftest:          # tiny stand-in workload, index built by the oracle-backed binary
-        args.genome_mb = min(args.genome_mb, 1) or 1; args.reads = min(args.reads, 2000); args.no_extra_legs = True; args.no_cpu_baseline = True; args.no_exclusive = True
+        args.genome_mb = min(args.genome_mb, 1) or 1; args.reads = min(args.reads, 2000); args.no_extra_legs = True; args.no_exclusive = True
     mb = args.genome_mb
     n_total = (args.steps + args.warmup) * args.reads
+    t_prep = time.time()
     if rank == 0:
         g, ginfo = build_genome(args, mb, log)
     barrier()
@@ -566,6 +577,7 @@ def main():
     t = time.time()
     fq = make_reads(args, g, run_dir, "reads_r%d" % rank, n_total, 7000 + rank)
     log("rank %d: %d pairs of reads in %.1f s" % (rank, n_total, time.time() - t))
+    data_prep_s = time.time() - t_prep
     outp = os.path.join(run_dir, "gpu_r%d_" % rank)
     ncpu_eff = effective_cpus()
     threads = args.host_threads or max(4, min(64, ncpu_eff // world))
@@ -639,9 +651,9 @@ def main():
     if dist is not None:
         dist.destroy_process_group()
     # ---- kernel times for the roofline: ONE engine context (a launch has the GPU to itself); the timed region overlaps the launches of two contexts, so
-    # the HIP events around a launch there also cover the time slices of the other context's kernels
+    # the HIP events around a launch there also cover the time slices of the other context's kernels (--full only: a run of its own)
     kms, kms_src = ms, "timed region (%d engine context(s))" % n_ctx
-    if world == 1 and not args.no_exclusive and n_ctx > max(1, int(rep.nDevices)):
+    if args.full and world == 1 and not args.no_exclusive and n_ctx > max(1, int(rep.nDevices)):
         try:
             ex = exclusive_leg(args, idx, fq, run_dir, threads)
             extra["kernel_ms_exclusive"] = ex
@@ -698,8 +710,10 @@ def main():
     }
     if selftest:
         line["selftest"] = "plumbing test on CPU (oracle behind the front end, gloo): NOT a measurement"
+    line["full"] = args.full
+    line["data_prep_s"] = round(data_prep_s, 1)            # genome + index + reads generated in this run, or ~0 when --workdir held them
     ref_prefix = os.path.join(run_dir, "cpu_")
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         try:
             cb = cpu_baseline(idx, fq, ref_prefix, n_total, log)
             extra["cpu_baseline"] = cb
@@ -718,7 +732,7 @@ def main():
     extra_path = os.path.join(args.workdir, "bench_extra.json")
     extra["notes"] = notes; extra["line"] = line
     json.dump(extra, open(extra_path, "w"))
-    if world == 1 and args.extra_legs and not args.no_extra_legs:
+    if world == 1 and args.extra_legs and not args.no_extra_legs:          # (parse: only with --full)
         left = args.budget_s - (time.time() - T_START)
         if left > 60:
             try:

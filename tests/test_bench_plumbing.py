@@ -8,7 +8,7 @@ import sys
 
 import pytest
 
-from util import ROOT
+from util import ROOT, refstar
 
 BENCH = os.path.join(ROOT, "bench.py")
 pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(ROOT, "oracle", "_build", "libstaramd_cli_oracle.so")), reason="oracle front end not built")
@@ -35,6 +35,7 @@ def test_line_is_compact_and_counts_ranks(gpus, tmp_path):
     for k in ("bound", "kernel", "achieved", "peak", "frac", "traffic", "kernel_ms", "algorithmic_bytes_per_launch"):
         assert k in d["roofline"]
     assert "selftest" in d                      # a CPU run can never pass for a measurement
+    assert d["full"] is False and "cpu_baseline" not in d and "full_size_parity" not in d      # a plain run: the headline only
     assert d["value"] > 0
     extra = json.load(open(d["extra"]))
     assert "counters_per_pair" in extra and "pipeline" in extra
@@ -69,6 +70,26 @@ def test_dump_outputs_are_the_last_step_and_repeat(tmp_path):
     ids = a["read_id.npy"]
     assert ids.min() >= 3 * 2000 and ids.max() < 4 * 2000           # the self-test maps 2000 pairs per step: ids 6000 .. 7999 are the last of 1 + 3 steps
     assert (a["pos.npy"] >= 0).all() and (a["ref.npy"] >= -1).all()
+
+
+def test_full_run_and_its_legs(tmp_path):
+    """--full runs the timed path of a plain run, then the reference on the same index and FASTQ (cpu_baseline) and the full-size parity against it
+    (a plain run does neither: test_line_is_compact_and_counts_ranks); the optional legs run only behind --full"""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    p = subprocess.run([sys.executable, BENCH, "--cpu-selftest", "--full", "--steps", "2", "--warmup", "1", "--workdir", str(tmp_path)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d, n = _line(p.stdout)
+    assert n < 4000 and d["full"] is True and d["steps"] == 2 and d["value"] > 0
+    assert "cpu_baseline" in d and "full_size_parity" in d
+    if refstar.have_ref():
+        assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["kind"] == "reference"
+        fp = d["full_size_parity"]
+        assert fp["sam_records_star_amd"] > 0 and fp["sam_multiset_identical"] and fp["sj_out_tab_identical"] and fp["log_final_counters_identical"], fp
+    else:                                       # oracle/_ref/STAR not built: the leg ran and says why it has no figure
+        assert "error" in d["cpu_baseline"] and d["full_size_parity"] is None
+    p = subprocess.run([sys.executable, BENCH, "--cpu-selftest", "--extra-legs", "--workdir", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, env=env)
+    assert p.returncode != 0 and "--full" in p.stderr and p.stdout.strip() == ""
 
 
 def test_world_size_must_match_gpus(tmp_path):

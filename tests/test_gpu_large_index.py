@@ -47,7 +47,7 @@ def _run(work):
 def test_100mb_index_two_pass_against_the_reference(tmp_path, built):
     """config 4 pinned in the GPU suite at a size where coordinates and the junction count are not toy-sized: --twopassMode Basic on a 100 Mb index with
     annotation, 100 k pairs -- the 1st pass's junctions inserted into the index resident in HBM -- against the reference's own 2-pass run: SAM multiset, SJ.out.tab
-    (column 6), the inserted junction list, Log.final.out counters (bench.py:two_pass_parity is the same at 400 Mb in every default bench run)"""
+    (column 6), the inserted junction list, Log.final.out counters (bench.py:two_pass_parity is the same at 400 Mb in bench.py --full --extra-legs)"""
     sys.path.insert(0, ROOT)
     import shutil
     import tempfile

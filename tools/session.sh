@@ -10,7 +10,7 @@
 #   tools/session.sh tests <tag> [pytest args]                 the GPU suite (default: tests -m gpu) + the hardware fuzzer (80 combinations)
 #   tools/session.sh measure <tag>                             tools/measure_session.sh: plain bench + rocprofv3 --stats + PMC passes (sq1, fetch, write) + gather ceiling;
 #                                                              afterwards, here: tools/make_traffic_json.py gpurun_out/<tag> 3100 400000 profiles/rNN_pmc_hbm_traffic.json
-#   tools/session.sh final <tag>                               the default bench run (CPU baseline, full-size parity, optional legs) + the whole GPU suite
+#   tools/session.sh final <tag>                               bench.py --full (CPU baseline, full-size parity) + the whole GPU suite
 cd ${GRAFT_REPO_ROOT:-.}
 mode=$1; tag=${2:-s}; shift 2
 O=gpurun_out/$tag; mkdir -p $O
@@ -35,8 +35,9 @@ PY
   measure)
     bash tools/measure_session.sh $tag 3100 3 "stats sq1 fetch write" > $O.log 2>&1; tail -12 $O.log ;;
   final)
-    timeout 1500 python bench.py > $O/bench_line.json 2> $O/bench.err; echo "bench rc $?"; cut -c1-800 $O/bench_line.json
+    timeout -k 10 1500 python bench.py --full > $O/bench_line.json 2> $O/bench.err; rc=$?; echo "bench rc $rc"; cut -c1-800 $O/bench_line.json
+    [ $rc = 0 ] || exit $rc                                    # nothing more on the GPU after a failed, faulted or timed-out bench
     cp /dev/shm/star_amd_bench/bench_extra.json $O/bench_extra.json 2>/dev/null
-    timeout 1200 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest rc $?"; tail -3 $O/pytest_gpu.log ;;
+    timeout -k 10 1200 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest rc $?"; tail -3 $O/pytest_gpu.log ;;
   *) echo "modes: ab e2e tests measure final"; exit 2 ;;
 esac
