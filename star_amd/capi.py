@@ -220,6 +220,7 @@ def engine_lib():
         L.staramd_prefetch_batch.restype = C.c_int; L.staramd_prefetch_batch.argtypes = [C.c_void_p, C.POINTER(Batch)]
         L.staramd_prefetch_cancel.restype = C.c_int; L.staramd_prefetch_cancel.argtypes = [C.c_void_p]
         L.staramd_prefetch_hits.restype = C.c_uint64; L.staramd_prefetch_hits.argtypes = [C.c_void_p]
+        L.staramd_overlapped_batches.restype = C.c_uint64; L.staramd_overlapped_batches.argtypes = [C.c_void_p]
         _engine = L
     return _engine
 
@@ -382,6 +383,9 @@ class Engine:
 
     def prefetch_hits(self):
         return self.L.staramd_prefetch_hits(self.ctx)
+
+    def overlapped_batches(self):
+        return self.L.staramd_overlapped_batches(self.ctx)
 
     def launch_count(self):
         return self.L.staramd_launch_count(self.ctx)

@@ -12,7 +12,6 @@
 #include <cmath>
 #include <string>
 #include <vector>
-#include <mutex>
 
 extern "C" __global__ void k_seed_search(const DevIndex *X, DevBatch B, DSeed *scratch, u32 scratchPerLane, const u32 *inList);
 extern "C" __global__ void k_seed_plan(const DevIndex *X, DevBatch B, SeedWork W);
@@ -72,9 +71,9 @@ struct staramd_ctx {
     int cur = 0; hipStream_t copyStream = nullptr;
     u32 *dPacked = nullptr; u32 packWordsCap = 0;
     int nCU = 256;
-    // seed kernel: one lane per read
+    // seed stage: lane = unit (k_seed_plan / k_seed_units / k_seed_merge); the reads they hand on take k_seed_search, one lane per read
     u32 seedLanes = 0; DSeed *scrSeed = nullptr; u32 seedPerLane = 0;
-    SeedWork seedWork = {}; u32 seedUnits = 1, seedUnitLanes = 0;      // lane = unit mapping of the seed stage (STARAMD_SEED_UNITS=0: lane = read, k_seed_search over every read)
+    SeedWork seedWork = {}; u32 seedUnitLanes = 0;
     // window kernel: one wave per read; fast pass (table in LDS) + big pass (reference limits, table in global memory)
     // the batch whose results did not fit the caller's arrays (STARAMD_ERR_RESULT_OVERFLOW): they stay resident; the same batch handed in again by the NEXT call is copied out,
     // not mapped again.  Valid only while nothing has run on this context (nLaunches) and nothing has changed what a map computes (stateGen) since the overflow.
@@ -103,7 +102,6 @@ struct staramd_ctx {
     u32 prune = 15;                       // STARAMD_PRUNE: bit 0 = window pruning, bit 1 = two-mate windows of a light read first, bit 2 = single-mate leaves of two-mate windows skipped (5.6),
                                           // bit 3 = pruning under resultSelect 2 as well: reads whose best alignment cannot be the main segment of a chimera (5.8)
     u32 ldsLimit = 65536;                 // dynamic LDS a block may ask for
-    u32 kernelTurns = 0;                  // STARAMD_KERNEL_TURNS=1: the kernel phase of a batch is serialised over the contexts of a device (runDevice); off: measured no gain
     u32 *dTrBase = nullptr, *dExBase = nullptr, *dTotals = nullptr, *dBlockTot = nullptr;
     staramd_read_result *dOutReads = nullptr; staramd_transcript *dOutTr = nullptr; staramd_exon *dOutEx = nullptr;
     hipEvent_t ev[10];
@@ -124,25 +122,6 @@ static void stateChanged(staramd_ctx *c) { c->stateGen++; for (staramd_ctx *s : 
 #define OWNER_ONLY(c) do { if ((c)->owner) { g_err = "this context shares the index of another one (staramd_create_shared): change the index through its owner"; return STARAMD_ERR_ARG; } } while (0)
 
 static u32 envU32(const char *name, u32 dflt) { const char *s = getenv(name); return s ? (u32)strtoul(s, nullptr, 10) : dflt; }
-// Streams.  The copies of this runtime are shader kernels (rocprofv3: __amd_rocclr_copyBuffer; no SDMA engine is used on this pool), so a copy that is to run BESIDE the
-// persistent kernels of the next batch needs compute units those kernels do not hold: with STARAMD_COPY_CUS = k > 0 the copy stream of a context is confined to the last k
-// CUs of the device and its kernel stream to the others (hipExtStreamCreateWithCUMask).  The kernels lose k / nCU of the chip; the result copy of batch i then completes
-// ~2 ms after its kernels while batch i + 1 runs (staramd_map_end), instead of behind them.  0 (or a runtime that refuses the mask): plain streams.
-static hipError_t makeStream(staramd_ctx *c, hipStream_t *s, bool copySide) {
-    const u32 k = envU32("STARAMD_COPY_CUS", 0), n = (u32)c->nCU;
-    if (k > 0 && k < n) {
-        std::vector<uint32_t> mask((n + 31) / 32, 0u);
-        for (u32 i = 0; i < n; i++) if ((i >= n - k) == copySide) mask[i >> 5] |= 1u << (i & 31u);
-        if (hipExtStreamCreateWithCUMask(s, (uint32_t)mask.size(), mask.data()) == hipSuccess) {
-            if (getenv("STARAMD_VERBOSE")) fprintf(stderr, "staramd: %s stream confined to %u of %u CUs\n", copySide ? "copy" : "kernel", copySide ? k : n - k, n);
-            return hipSuccess;
-        }
-        (void)hipGetLastError();
-        if (getenv("STARAMD_VERBOSE")) fprintf(stderr, "staramd: hipExtStreamCreateWithCUMask refused, plain stream\n");
-    }
-    return hipStreamCreate(s);
-}
-
 template <class T> static int devAlloc(std::vector<void *> &reg, T **p, u64 n) {
     void *q = nullptr;
     hipError_t e = hipMalloc(&q, std::max<u64>(n * sizeof(T), 16));
@@ -337,14 +316,12 @@ static int allocWork(staramd_ctx *c) {
     if ((rc = devAlloc(R, &c->dMate1, (u64)N))) return rc;
     if ((rc = devAlloc(R, &c->dMM, (u64)N))) return rc;
     c->in[0].bases = c->dBases; c->in[0].readOffset = c->dReadOffset; c->in[0].mate1 = c->dMate1; c->in[0].mm = c->dMM; c->cur = 0;
-    if (envU32("STARAMD_PREFETCH", 1)) {
-        u8 *raw = nullptr; if ((rc = devAlloc(R, &raw, c->maxBases + 192))) return rc; if (hipMemset(raw, 4, c->maxBases + 192) != hipSuccess) { g_err = "hipMemset failed"; return STARAMD_ERR_DEVICE; } c->in[1].bases = raw + 64;
-        if ((rc = devAlloc(R, &c->in[1].readOffset, (u64)N + 1))) return rc;
-        if ((rc = devAlloc(R, &c->in[1].mate1, (u64)N))) return rc;
-        if ((rc = devAlloc(R, &c->in[1].mm, (u64)N))) return rc;
-        if (makeStream(c, &c->copyStream, true) != hipSuccess) { g_err = "hipStreamCreate failed"; return STARAMD_ERR_DEVICE; }
-        for (int k = 0; k < 2; k++) if (hipEventCreateWithFlags(&c->in[k].up, hipEventDisableTiming) != hipSuccess) { g_err = "hipEventCreate failed"; return STARAMD_ERR_DEVICE; }
-    }
+    { u8 *raw = nullptr; if ((rc = devAlloc(R, &raw, c->maxBases + 192))) return rc; if (hipMemset(raw, 4, c->maxBases + 192) != hipSuccess) { g_err = "hipMemset failed"; return STARAMD_ERR_DEVICE; } c->in[1].bases = raw + 64; }
+    if ((rc = devAlloc(R, &c->in[1].readOffset, (u64)N + 1))) return rc;
+    if ((rc = devAlloc(R, &c->in[1].mate1, (u64)N))) return rc;
+    if ((rc = devAlloc(R, &c->in[1].mm, (u64)N))) return rc;
+    if (hipStreamCreate(&c->copyStream) != hipSuccess) { g_err = "hipStreamCreate failed"; return STARAMD_ERR_DEVICE; }
+    for (int k = 0; k < 2; k++) if (hipEventCreateWithFlags(&c->in[k].up, hipEventDisableTiming) != hipSuccess) { g_err = "hipEventCreate failed"; return STARAMD_ERR_DEVICE; }
     c->packWordsCap = 0;
     DevBatch &B = c->B; memset(&B, 0, sizeof(B));
     B.bases = c->dBases; B.readOffset = c->dReadOffset; B.mate1Length = c->dMate1; B.mmMaxTotal = c->dMM;
@@ -382,35 +359,29 @@ static int allocWork(staramd_ctx *c) {
     if ((rc = devAlloc(R, &c->dOutEx, (u64)B.exCap))) return rc;
     if (hipHostMalloc((void **)&c->hostScratch, (64 + CUR_N) * sizeof(u32) + DC_N * sizeof(u64)) != hipSuccess) { g_err = "hipHostMalloc failed"; return STARAMD_ERR_DEVICE; }
     const staramd_params &P = c->X.P;
-    // ---- seed kernel: one lane per read, PC table per lane sized by the reference's seedPerReadNmax
+    // ---- seed stage: a lane per unit of the search schedule (k_seed_plan / k_seed_units / k_seed_merge).  2x101 has 12 groups / 10 units per pair, 2x150 16 / 14; a read
+    // that does not fit what is left of the pools takes k_seed_search (no regrowth, no re-run): at most 64 blocks, each lane with a PC table sized by seedPerReadNmax
     int seedPerCU = 2;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&seedPerCU, k_seed_search, 256, 0) != hipSuccess || seedPerCU < 1) seedPerCU = 2;
-    u32 lanes = envU32("STARAMD_SEED_LANES", (u32)c->nCU * (u32)seedPerCU * 256u);
-    lanes = std::max<u32>(256, std::min<u32>(lanes, ((N + 255) / 256) * 256));
-    c->seedLanes = (lanes / 256) * 256;
+    c->seedLanes = std::min<u32>(64u, (N + 255) / 256) * 256u;
     c->seedPerLane = P.seedPerReadNmax + 1;
     if ((rc = devAlloc(R, &c->scrSeed, (u64)c->seedLanes * c->seedPerLane))) return rc;
-    // 0: a lane per read (k_seed_search over every read); 1: a lane per unit of the search schedule (k_seed_plan / k_seed_units / k_seed_merge)
-    c->seedUnits = envU32("STARAMD_SEED_UNITS", 1);
-    if (c->seedUnits) {
-        // 2x101 has 12 groups / 10 units per pair, 2x150 16 / 14; a read that does not fit what is left of the pools takes k_seed_search (no regrowth, no re-run)
-        SeedWork &W = c->seedWork;
-        W.groupCap = (u32)std::min<u64>((u64)N * envU32("STARAMD_SEED_GROUPS_PER_READ", 20) + 256, 0xFFFFFFF0ull);
-        W.unitCap = (u32)std::min<u64>((u64)N * envU32("STARAMD_SEED_GROUPS_PER_READ", 20) + 256, 0xFFFFFFF0ull);
-        W.slotLimit = std::min<u32>(SEED_SLOTS, std::max<u32>(1, envU32("STARAMD_SEED_SLOT_LIMIT", SEED_SLOTS)));
-        if ((rc = devAlloc(R, &W.units, (u64)W.unitCap))) return rc;
-        if ((rc = devAlloc(R, &W.slots, (u64)W.groupCap * SEED_SLOTS))) return rc;
-        if ((rc = devAlloc(R, &W.groupHead, (u64)W.groupCap))) return rc;
-        if ((rc = devAlloc(R, &W.plan, (u64)N))) return rc;
-        if ((rc = devAlloc(R, &W.handOn, (u64)N))) return rc;
-        int upCU = seedPerCU;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&upCU, k_seed_units, 256, 0) != hipSuccess || upCU < 1) upCU = seedPerCU;
-        c->seedUnitLanes = envU32("STARAMD_SEED_UNIT_LANES", (u32)c->nCU * (u32)upCU * 256u) / 256u * 256u;
-        if (c->seedUnitLanes < 256) c->seedUnitLanes = 256;
-    }
+    SeedWork &W = c->seedWork;
+    W.groupCap = (u32)std::min<u64>((u64)N * envU32("STARAMD_SEED_GROUPS_PER_READ", 20) + 256, 0xFFFFFFF0ull);
+    W.unitCap = (u32)std::min<u64>((u64)N * envU32("STARAMD_SEED_GROUPS_PER_READ", 20) + 256, 0xFFFFFFF0ull);
+    W.slotLimit = std::min<u32>(SEED_SLOTS, std::max<u32>(1, envU32("STARAMD_SEED_SLOT_LIMIT", SEED_SLOTS)));
+    if ((rc = devAlloc(R, &W.units, (u64)W.unitCap))) return rc;
+    if ((rc = devAlloc(R, &W.slots, (u64)W.groupCap * SEED_SLOTS))) return rc;
+    if ((rc = devAlloc(R, &W.groupHead, (u64)W.groupCap))) return rc;
+    if ((rc = devAlloc(R, &W.plan, (u64)N))) return rc;
+    if ((rc = devAlloc(R, &W.handOn, (u64)N))) return rc;
+    int upCU = seedPerCU;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&upCU, k_seed_units, 256, 0) != hipSuccess || upCU < 1) upCU = seedPerCU;
+    c->seedUnitLanes = envU32("STARAMD_SEED_UNIT_LANES", (u32)c->nCU * (u32)upCU * 256u) / 256u * 256u;
+    if (c->seedUnitLanes < 256) c->seedUnitLanes = 256;
     // ---- window kernel
     c->lightEst = envU32("STARAMD_LIGHT_EST", 65536);
-    c->prune = envU32("STARAMD_PRUNE", 15); c->kernelTurns = envU32("STARAMD_KERNEL_TURNS", 0); c->laneClass = envU32("STARAMD_LANE_CLASS", 0);          // (knobs are read here, once: not on the launch path)
+    c->prune = envU32("STARAMD_PRUNE", 15); c->laneClass = envU32("STARAMD_LANE_CLASS", 0);          // (knobs are read here, once: not on the launch path)
     if (prop.sharedMemPerBlock >= 16384) c->ldsLimit = (u32)std::min<size_t>(prop.sharedMemPerBlock, 65536);
     // first launch: 128 table rows + 512 owner-map slots = 6 KB of LDS per wavefront, 6 blocks of 4 wavefronts per CU (k_windows is held to 6 waves per SIMD)
     c->capW = envU32("STARAMD_CAP_WINDOWS", 128); c->capBlocks = envU32("STARAMD_CAP_WA_BLOCKS", 128);
@@ -506,9 +477,9 @@ extern "C" int staramd_create(staramd_ctx **out, int device, const staramd_genom
     c->device = device; c->maxReads = maxBatchReads; c->maxBases = maxBatchBases ? maxBatchBases : (u64)maxBatchReads * (STARAMD_READ_LEN_MAX + 1);
     int rc = uploadIndex(c, g, p);
     if (!rc) rc = allocWork(c);
-    if (!rc) { if (makeStream(c, &c->stream, false) != hipSuccess) { g_err = "hipStreamCreate failed"; rc = STARAMD_ERR_DEVICE; } }
+    if (!rc) { if (hipStreamCreate(&c->stream) != hipSuccess) { g_err = "hipStreamCreate failed"; rc = STARAMD_ERR_DEVICE; } }
     if (!rc) for (int i = 0; i < 10; i++) if (hipEventCreate(&c->ev[i]) != hipSuccess) { g_err = "hipEventCreate failed"; rc = STARAMD_ERR_DEVICE; }
-    if (!rc && !getenv("STARAMD_SPIN_WAIT") && hipEventCreateWithFlags(&c->evWait, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) c->evWait = nullptr;
+    if (!rc && hipEventCreateWithFlags(&c->evWait, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) c->evWait = nullptr;
     if (!rc && hipEventCreateWithFlags(&c->evDownload, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { g_err = "hipEventCreate failed"; rc = STARAMD_ERR_DEVICE; }
     if (rc) { freeAll(c->indexAllocs); freeAll(c->workAllocs); delete c; return rc; }
     memset(c->counters, 0, sizeof(c->counters));
@@ -524,9 +495,9 @@ extern "C" int staramd_create_shared(staramd_ctx **out, staramd_ctx *owner, uint
     c->device = owner->device; c->maxReads = maxBatchReads; c->maxBases = maxBatchBases ? maxBatchBases : (u64)maxBatchReads * (STARAMD_READ_LEN_MAX + 1);
     c->owner = owner; c->X = owner->X; c->dX = owner->dX;
     int rc = allocWork(c);
-    if (!rc) { if (makeStream(c, &c->stream, false) != hipSuccess) { g_err = "hipStreamCreate failed"; rc = STARAMD_ERR_DEVICE; } }
+    if (!rc) { if (hipStreamCreate(&c->stream) != hipSuccess) { g_err = "hipStreamCreate failed"; rc = STARAMD_ERR_DEVICE; } }
     if (!rc) for (int i = 0; i < 10; i++) if (hipEventCreate(&c->ev[i]) != hipSuccess) { g_err = "hipEventCreate failed"; rc = STARAMD_ERR_DEVICE; }
-    if (!rc && !getenv("STARAMD_SPIN_WAIT") && hipEventCreateWithFlags(&c->evWait, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) c->evWait = nullptr;
+    if (!rc && hipEventCreateWithFlags(&c->evWait, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) c->evWait = nullptr;
     if (!rc && hipEventCreateWithFlags(&c->evDownload, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { g_err = "hipEventCreate failed"; rc = STARAMD_ERR_DEVICE; }
     if (rc) { freeAll(c->workAllocs); delete c; return rc; }
     memset(c->counters, 0, sizeof(c->counters));
@@ -727,16 +698,10 @@ static int enqueueAll(staramd_ctx *c) {
     dim3 block(256);
     u32 ldsWords = ((c->residentMaxLread + 7) / 8) | 1u;              // odd stride: conflict-free LDS staging
     HIPCHK(hipEventRecord(c->ev[0], s));
-    {
-        u32 lanes = std::min<u32>(c->seedLanes, ((n + 255) / 256) * 256);
-        if (c->seedUnits) {
-            hipLaunchKernelGGL(k_seed_plan, dim3((n + 255) / 256), block, 0, s, c->dX, B, c->seedWork);
-            hipLaunchKernelGGL(k_seed_units, dim3(c->seedUnitLanes / 256), block, 0, s, c->dX, B, c->seedWork);
-            hipLaunchKernelGGL(k_seed_merge, dim3(std::min<u32>((n + 3) / 4, (u32)c->nCU * 8u)), block, 0, s, c->dX, B, c->seedWork);
-            hipLaunchKernelGGL(k_seed_search, dim3(std::min<u32>(lanes / 256, 64u)), block, 0, s, c->dX, B, c->scrSeed, c->seedPerLane, (const u32 *)c->seedWork.handOn);      // what the units handed on (rarely anything)
-        } else
-        hipLaunchKernelGGL(k_seed_search, dim3(lanes / 256), block, 0, s, c->dX, B, c->scrSeed, c->seedPerLane, (const u32 *)nullptr);
-    }
+    hipLaunchKernelGGL(k_seed_plan, dim3((n + 255) / 256), block, 0, s, c->dX, B, c->seedWork);
+    hipLaunchKernelGGL(k_seed_units, dim3(c->seedUnitLanes / 256), block, 0, s, c->dX, B, c->seedWork);
+    hipLaunchKernelGGL(k_seed_merge, dim3(std::min<u32>((n + 3) / 4, (u32)c->nCU * 8u)), block, 0, s, c->dX, B, c->seedWork);
+    hipLaunchKernelGGL(k_seed_search, dim3(std::min<u32>(c->seedLanes / 256, (n + 255) / 256)), block, 0, s, c->dX, B, c->scrSeed, c->seedPerLane, (const u32 *)c->seedWork.handOn);      // what the units handed on (rarely anything)
     HIPCHK(hipEventRecord(c->ev[1], s));
     {
         u32 blocks = std::max<u32>(1, std::min<u32>(c->winBlocks, (n + 3) / 4));
@@ -829,12 +794,6 @@ static int launchAll(staramd_ctx *c, staramd_results *r, u32 *flagsOut) {
     return rc ? rc : collectAll(c, r, flagsOut);
 }
 
-// The kernels of the engine are persistent launches sized to fill the GPU: when two contexts of one device (the front end runs two, so that the copies of one
-// batch overlap with the kernels of the other) have their launches in flight at the same time they do not run side by side, they take each other's CUs -- every
-// kernel stretches, and the short ones (k_stitch_verify: 1 ms alone) wait 5-7 ms for a CU behind the other context's persistent blocks (rocprofv3 timeline,
-// profiles/r04_timeline_two_contexts.txt).  STARAMD_KERNEL_TURNS=1 takes the KERNEL phase of a batch in turns per device (uploads before it and result copies after it
-// still overlap with the other context's kernels).  Measured, alternating runs on one box: 6.65 M pairs/s with turns, 6.82 without, 6.78 with ONE context -- the front end
-// runs one context per GPU by default now, and the knob stays off.
 // the result arrays of the batch that was mapped last, into the caller's: totals first -- arrays that are too small are an error return, and the results stay where they are
 static int copyResults(staramd_ctx *c, staramd_results *r) {
     DevBatch &B = c->B; hipStream_t s = c->stream; const u32 n = B.nReads;
@@ -847,15 +806,12 @@ static int copyResults(staramd_ctx *c, staramd_results *r) {
     HIPCHK(waitStream(c));
     return STARAMD_OK;
 }
-static std::mutex g_kernelTurn[64];
 static int runDevice(staramd_ctx *c, staramd_results *r) {
     DevBatch &B = c->B; hipStream_t s = c->stream;
     u32 n = B.nReads;
     u32 flags = 0;
     for (int attempt = 0;; attempt++) {
-        int rc;
-        if (c->kernelTurns) { std::lock_guard<std::mutex> turn(g_kernelTurn[c->device & 63]); rc = launchAll(c, r, &flags); }
-        else rc = launchAll(c, r, &flags);
+        int rc = launchAll(c, r, &flags);
         if (rc) return rc;
         if (flags == 0) break;
         const u32 *cur = c->hostScratch + 8;
@@ -873,7 +829,7 @@ static int runDevice(staramd_ctx *c, staramd_results *r) {
 
 // an upload that was started for a batch which will not be mapped: waited for and forgotten (the sets are free again)
 static void dropPrefetched(staramd_ctx *c) {
-    if (!c->copyStream || (!c->in[0].pending && !c->in[1].pending)) return;
+    if (!c->in[0].pending && !c->in[1].pending) return;
     (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->copyStream);
     c->in[0].pending = c->in[1].pending = false;
 }
@@ -911,7 +867,7 @@ static int stageBatch(staramd_ctx *c, const staramd_batch *b) {
             HIPCHK(hipStreamWaitEvent(s, c->in[use].up, 0));
             c->nPrefetchHits++;
         } else {                    // not prefetched: into the set that holds nothing pending (both pending: the older one is given up)
-            use = !c->in[c->cur].pending ? c->cur : (c->copyStream && !c->in[1 - c->cur].pending ? 1 - c->cur : c->cur);
+            use = !c->in[c->cur].pending ? c->cur : (!c->in[1 - c->cur].pending ? 1 - c->cur : c->cur);
             staramd_ctx::InSet &I = c->in[use];
             if (I.pending) HIPCHK(hipStreamSynchronize(c->copyStream));          // (an upload nobody asked for any more may still be writing into the set)
             HIPCHK(hipMemcpyAsync(I.bases, b->bases + base0, nBases, hipMemcpyHostToDevice, s));
@@ -1018,12 +974,12 @@ extern "C" int staramd_map_end(staramd_ctx *c, staramd_results *r, const staramd
     r->trCount = totals[0]; r->exCount = totals[1];
     if (totals[0] > r->trCapacity || totals[1] > r->exCapacity) { g_err = "result arrays too small: need " + std::to_string(totals[0]) + " transcripts, " + std::to_string(totals[1]) + " exons"; return STARAMD_ERR_RESULT_OVERFLOW; }   // (the batch stays in flight: call again with larger arrays)
     // the results leave on the copy stream; the kernels of `next` start beside them (its k_gather, the only writer of dOut*, waits for the copy)
-    hipStream_t cs = c->copyStream ? c->copyStream : c->stream;
+    hipStream_t cs = c->copyStream;
     HIPCHK(hipMemcpyAsync(r->reads, c->dOutReads, (u64)n * sizeof(staramd_read_result), hipMemcpyDeviceToHost, cs));
     if (totals[0]) HIPCHK(hipMemcpyAsync(r->tr, c->dOutTr, (u64)totals[0] * sizeof(staramd_transcript), hipMemcpyDeviceToHost, cs));
     if (totals[1]) HIPCHK(hipMemcpyAsync(r->ex, c->dOutEx, (u64)totals[1] * sizeof(staramd_exon), hipMemcpyDeviceToHost, cs));
     HIPCHK(hipEventRecord(c->evDownload, cs));
-    c->downloadPending = c->copyStream != nullptr;
+    c->downloadPending = true;
     c->inFlight = false; c->collected = false;
     int rcNext = STARAMD_OK;
     if (next && next->nReads) { rcNext = staramd_map_begin(c, next); if (!rcNext) c->nOverlapped++; }
@@ -1036,7 +992,7 @@ extern "C" uint32_t staramd_capabilities(void) { return STARAMD_CAP_CHIM_SELECT;
 
 extern "C" int staramd_prefetch_batch(staramd_ctx *c, const staramd_batch *b) {
     if (!c || !b) { g_err = "bad arguments"; return STARAMD_ERR_ARG; }
-    if (!c->copyStream || b->nReads == 0 || b->readOffset[0] != 0) return STARAMD_OK;      // prefetch off, or a batch that map_batch rebases: uploaded there
+    if (b->nReads == 0 || b->readOffset[0] != 0) return STARAMD_OK;                        // nothing, or a batch that map_batch rebases: uploaded there
     const u64 nBases = b->readOffset[b->nReads];
     if (b->nReads > c->maxReads || nBases > c->maxBases) return STARAMD_OK;                // (map_batch reports it)
     // the set that holds nothing pending: the one the last mapped batch used (that call has returned), unless the other one is free too

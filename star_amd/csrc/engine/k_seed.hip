@@ -370,7 +370,7 @@ __device__ __forceinline__ void addCounters(DevBatch &B, const SeedCnt &cn) {
                             // (profiles/r06_ab_session6_*); without the keys 8 was 10 % faster than 4 (round 3)
 #endif
 // the whole nest of one read on one lane: the general form (any number of pieces, start points and seeds per search).  Runs over the reads of `inList`
-// (B.cursors[CUR_OVF_SEED] of them: what the unit mapping below handed on), or over every read when inList is null (STARAMD_SEED_UNITS=0)
+// (B.cursors[CUR_OVF_SEED] of them: what the unit mapping below handed on)
 extern "C" __global__ void __launch_bounds__(256, SEED_WAVES) k_seed_search(const DevIndex *__restrict__ Xp, DevBatch B, DSeed *scratch, u32 scratchPerLane, const u32 *inList) {
     const DevIndex &X = *Xp;
     u32 lane = blockIdx.x * blockDim.x + threadIdx.x;
@@ -378,12 +378,12 @@ extern "C" __global__ void __launch_bounds__(256, SEED_WAVES) k_seed_search(cons
     StoreNow sink{X, st};
     SeedCnt cn = {0, 0, 0}; u64 nSeedsTot = 0;
     const staramd_params &P = X.P;
-    const u32 nItems = inList ? B.cursors[CUR_OVF_SEED] : B.nReads;
+    const u32 nItems = B.cursors[CUR_OVF_SEED];
     for (;;) {
         if (*(volatile u32 *)&B.cursors[CUR_TICKET_SEED] >= nItems) break;          // (a lane that comes for nothing does not queue for the counter)
         u32 it = atomicAdd(&B.cursors[CUR_TICKET_SEED], 1u);
         if (it >= nItems) break;
-        const u32 ir = inList ? inList[it] : it;
+        const u32 ir = inList[it];
         const u8 *R = B.bases + B.readOffset[ir];
         u32 Lread = (u32)(B.readOffset[ir + 1] - B.readOffset[ir]);
         st.nP = 0; st.nA = 0; st.multNmin = 0; st.multNminL = 0; st.fatal = false;

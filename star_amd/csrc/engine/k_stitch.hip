@@ -594,9 +594,6 @@ __device__ __forceinline__ i32 leafNeedScore(const StitchCtx &c, const staramd_p
 // extensions can reach (they stop at the mate spacer and at the ends of the read) + the largest value of the genomic-length term
 __device__ __forceinline__ bool leafCanCount(const StitchCtx &c, const DevIndex &X, const Hdr &h, const WinRec &wr, const u32 fragFirst, const u32 fragLast) {
     const staramd_params &P = X.P;
-#ifdef STARAMD_NO_LEAF_BOUND           // A/B builds (tools/build_variants.sh): without test (a)
-    return true;
-#endif
     if (P.chimSegmentMinPositive) return true;
     const u32 Lread = c.Lread;
     const u32 spacer = c.readLength[0] < Lread ? (c.str == 0 ? c.readLength[0] : Lread - 1u - c.readLength[0]) : Lread;       // position of the mate spacer in R[] (none: Lread)
@@ -660,9 +657,7 @@ __device__ static void finalizeTranscript(StitchCtx &c, u32 lane, Hdr h, const L
         Score += X.glScoreAt1 + X.glStep * (i32)nAbove;
         Score = max(0, Score);
     }
-#ifndef STARAMD_NO_LEAF_EARLY          // A/B builds: without test (b)
     if (Score < needScore && !P.chimSegmentMinPositive) { DIAG(c.nLeavesEarly++); return; }      // (b) of the note above: the final score is known, the filters cannot make it count
-#endif
     // ---- leaf filters (:83-219), lane = exon row: every lane holds one exon of the transcript in registers, neighbours
     // come over the DPP wave shift, sums are DPP reductions, "any exon fails" is a ballot
     staramd_exon xe;

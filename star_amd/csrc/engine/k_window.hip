@@ -29,12 +29,6 @@
 #define NOWIN 0xFFFFFFFFu
 static_assert(sizeof(DWin) == 16, "a window record is two 8-byte words (emission stores it as such)");
 static_assert(sizeof(DWA) == 24 && offsetof(DWA, iFrag) == 21, "a seed-list row is three 8-byte words, iFrag in byte 21 (emission)");
-#ifndef WIN_EMIT_LANES
-#define WIN_EMIT_LANES 1            // emission: windows of one or two seeds copied by a lane each (windowsBody)
-#endif
-#ifndef WIN_UNIQ
-#define WIN_UNIQ 1                  // one-locus seeds converted and looked up together (windowsBody)
-#endif
 #ifdef STARAMD_PROFILE
 #define WPROF_T0() u64 wprof_t0_ = __builtin_readcyclecounter()
 #define WPROF_MARK(k) { u64 t1_ = __builtin_readcyclecounter(); wprof[k] += t1_ - wprof_t0_; wprof_t0_ = t1_; }
@@ -335,9 +329,8 @@ template <bool BIG> __device__ __forceinline__ void windowsBody(const DevIndex *
         // Seeds of ONE locus outside the inserted junction sequences (12 of the 17 seeds of a pair) are converted here once, lane i = seed i -- strand flip, read
         // start, chromosome of the bin -- instead of one seed per trip of the loops of pass A and pass B with one lane at work: myA1 becomes the converted locus,
         // uInfo = 1 << 31 | strand << 30 | x << 16 | rStart as pass B wants it, x = the chromosome in pass A, the window + 1 in pass B (14 bits: genomes of up to
-        // 16 383 sequences; others keep the loops).  Both passes then take such a seed with two lane reads.  (WIN_UNIQ=0: A/B builds without.)
+        // 16 383 sequences; others keep the loops).  Both passes then take such a seed with two lane reads.
         u32 uInfo = 0;
-#if WIN_UNIQ
         if (lane < nPre && mySeed.nrep == 1u && X.nChrReal < 0x3FFFu) {
             u64 a1 = myA1; u32 aStr = (u32)(a1 >> X.strandBit); a1 &= X.strandMask;
             const u32 aL = mySeed.L; u32 aR = mySeed.rStart;
@@ -349,10 +342,8 @@ template <bool BIG> __device__ __forceinline__ void windowsBody(const DevIndex *
                 if (chr < 0x3FFFu) { myA1 = a1; uInfo = 0x80000000u | (aStr << 30) | (chr << 16) | (aR & 0xFFFFu); }
             }
         }
-#endif
         // ---- pass A: anchors (ReadAlign_stitchPieces.cpp:41-93)
         for (u32 iP = 0; iP < rd.nSeeds && !s.overflow; iP++) {
-#if WIN_UNIQ
             const u32 xInfo = laneGet32(uInfo, iP < nPre ? iP : 0u);
             if (iP < nPre && (xInfo & 0x80000000u)) {          // a seed converted above: its one locus goes straight into the replay
                 if (1u > P.winAnchorMultimapNmax) continue;
@@ -360,7 +351,6 @@ template <bool BIG> __device__ __forceinline__ void windowsBody(const DevIndex *
                 createExtendWindowsWithAlign(X, s, laneGet64(myA1, iP), (xInfo >> 30) & 1u, (xInfo >> 16) & 0x3FFFu, lane);
                 continue;
             }
-#endif
             const DSeed sd = iP < nPre ? seedOfLane(mySeed, iP) : PC[iP];
             const u64 preA1 = laneGet64(myA1, iP < nPre ? iP : 0u);
             if (sd.nrep > P.winAnchorMultimapNmax) continue;
@@ -450,16 +440,13 @@ template <bool BIG> __device__ __forceinline__ void windowsBody(const DevIndex *
         nWindows += s.nW;
         WPROF_MARK(1);
         // ---- pass B: all seeds (:129-185)
-#if WIN_UNIQ
         // the converted one-locus seeds look their windows up together (owner map only: the Bloom-filter form keeps them in the loop); window + 1 takes the chromosome's place
         const bool uniqB = s.ownMap && !s.overflow;
         if (uniqB && (uInfo & 0x80000000u)) {
             const u32 w = ownLookup(s.bitmap, s.ownMask, (u32)(myA1 >> P.winBinNbits) * 2u + ((uInfo >> 30) & 1u));
             uInfo = (uInfo & 0xC000FFFFu) | ((w == NOWIN ? 0u : w + 1u) << 16);
         }
-#endif
         for (u32 iP = 0; iP < rd.nSeeds && !s.overflow && !s.tooMany; iP++) {
-#if WIN_UNIQ
             const u32 xInfo = laneGet32(uInfo, iP < nPre ? iP : 0u);
             if (uniqB && iP < nPre && (xInfo & 0x80000000u)) {
                 nSAenum++;
@@ -471,7 +458,6 @@ template <bool BIG> __device__ __forceinline__ void windowsBody(const DevIndex *
                 assignAlignToWindow(X, s, w1 - 1u, laneGet64(myA1, iP), uL, 1u, (x4 >> 8) & 0xFFu, xInfo & 0xFFFFu, uAnchor, -1, lane);
                 continue;
             }
-#endif
             const DSeed sd = iP < nPre ? seedOfLane(mySeed, iP) : PC[iP];
             const u64 preA1 = laneGet64(myA1, iP < nPre ? iP : 0u);
             u32 aNrep = sd.nrep, aFrag = sd.iFrag, aLength = sd.L, aDir = sd.dir;
@@ -483,11 +469,8 @@ template <bool BIG> __device__ __forceinline__ void windowsBody(const DevIndex *
                 if (lane < cnt) {
                     a1 = (aNrep == 1u && iP < nPre) ? preA1 : packedGet(X.SA, sd.saStart + base + lane, X.saBits, X.saMask);
                     u32 aStr;
-#if WIN_UNIQ
                     if (iP < nPre && (xInfo & 0x80000000u)) { aStr = (xInfo >> 30) & 1u; aRstart = xInfo & 0xFFFFu; }       // (converted above; here because the read has no owner map)
-                    else
-#endif
-                    {
+                    else {
                         aStr = (u32)(a1 >> X.strandBit); a1 &= X.strandMask;
                         aRstart = sd.rStart;
                         if (aDir == 1 && aStr == 0) { aStr = 1; aRstart = s.Lread - (aLength + aRstart); }
@@ -565,7 +548,6 @@ template <bool BIG> __device__ __forceinline__ void windowsBody(const DevIndex *
             rdWinOffset = wo; rdNWin = nOut;
             const u32 ioRead = io;
             if (light && lane == 0) B.items[io] = 0x80000000u | ir;
-#if WIN_EMIT_LANES
             // Windows in index order get consecutive places in the pools.  One window per trip of a loop means one dependent round trip per window (its rows come from
             // the seed-list arena in global memory) -- twenty per pair, most of them for a window of one or two seeds.  So: lane = window; places by a prefix sum over the
             // lanes; a window of one or two rows is copied by its own lane (all of them in ONE round trip), the few longer lists by the whole wavefront as before.
@@ -603,22 +585,6 @@ template <bool BIG> __device__ __forceinline__ void windowsBody(const DevIndex *
                 const u32 totW = laneGet32(inclW, 63u), totA = laneGet32(inclA, 63u);
                 wo += totW; ao += totA; io += light ? 0u : totW;
             }
-#else
-            for (u32 j = 0; j < s.nW; j++) {
-                u32 n = s.t.nwa[j];
-                if (n == 0) continue;
-                u32 m = s.t.meta[j];
-                const DWA *A = s.arena + (u64)s.t.blk[j] * WA_MAX;
-                u8 fr = 0;
-                if (lane < n) { const DWA row = A[lane]; fr = row.iFrag; B.waPool[ao + lane] = row; }
-                const u8 mates = (u8)((__ballot(lane < n && fr == 0) ? 1u : 0u) | (__ballot(lane < n && fr != 0) ? 2u : 0u));
-                if (lane == 0) {
-                    DWin d; d.read = ir; d.chr = m >> 2; d.waOffset = ao; d.nWA = (u16)n; d.str = (u8)((m >> 1) & 1u); d.mates = mates; B.winPool[wo] = d;
-                    if (!light) { B.items[io] = wo; B.itemClass[io] = (u8)min(n + 1u, 31u); io++; }
-                }
-                wo++; ao += n;
-            }
-#endif
             if (light && lane == 0) {
                 // cost class of a light read = bits of its walk-size estimate (k_order_* sorts by it, k_stitch_lane takes the classes up to its cap)
                 const u32 cls = 32u - (u32)__clz((int)est);

@@ -69,9 +69,6 @@ __device__ __forceinline__ u8 GB(StitchCtx &c, u64 pos) { c.nGstitch++; return g
 //     singleBar = longest mate + perJ * (most seeds of any window of the read - 1) + range  <  best.
 // The same bar covers the single-mate leaves of a two-mate window that are not finalised (5.6) and the single-mate windows skipped after the two-mate ones (sweep 1).
 __device__ __forceinline__ i32 pruneSingleBar(const staramd_params &P, i32 perJ, u32 len0, u32 len1, u32 maxSeedsRead) {
-#ifdef STARAMD_PRUNE_SLACK_R5          // A/B builds: the slack of rounds 2-5 (as many junctions as a transcript has exon slots)
-    maxSeedsRead = STARAMD_MAX_N_EXONS;
-#endif
     const u32 nj = maxSeedsRead > 0 ? min(maxSeedsRead - 1u, (u32)STARAMD_MAX_N_EXONS - 1u) : 0u;
     return (i32)max(len0, len1) + perJ * (i32)nj + P.outFilterMultimapScoreRange;
 }

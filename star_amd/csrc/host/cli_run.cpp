@@ -56,7 +56,6 @@ struct Queue {                                   // hand-off between two pipelin
     void push(const Msg &x) { { std::lock_guard<std::mutex> l(m); q.push_back(x); } cv.notify_all(); }
     void close() { { std::lock_guard<std::mutex> l(m); closed = true; } cv.notify_all(); }
     bool pop(Msg &x) { std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return !q.empty() || closed; }); if (q.empty()) return false; x = q.front(); q.pop_front(); return true; }
-    bool tryPop(Msg &x) { std::lock_guard<std::mutex> l(m); if (q.empty()) return false; x = q.front(); q.pop_front(); return true; }        // what is waiting, without waiting for it
     bool peek(Msg &x) { std::lock_guard<std::mutex> l(m); if (q.empty()) return false; x = q.front(); return true; }          // what the next pop would hand out, if anything is waiting
 };
 struct Tokens {                                  // counting semaphore over a small set of buffer indices
@@ -64,7 +63,7 @@ struct Tokens {                                  // counting semaphore over a sm
     // the slot that was given back LAST is handed out first: a batch then lands in buffers (line tables, page-locked numeric arrays, result arrays) that were in use a
     // moment ago, and a slot is used for the first time (page faults and hipHostMalloc inside the reader) only when the pipeline really is that deep.  Round-robin order
     // went round all slots whatever the depth: 4.94 / 5.56 M pairs/s against 6.84 / 6.19 with the host stages alone on a GPU box (profiles/r04_host_stages_on_the_gpu_box.txt)
-    int take() { std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return !free.empty(); }); static const bool fifo = getenv("STARAMD_SLOTS_FIFO") != nullptr; int v = fifo ? free.front() : free.back(); if (fifo) free.pop_front(); else free.pop_back(); return v; }
+    int take() { std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return !free.empty(); }); int v = free.back(); free.pop_back(); return v; }
     void give(int v) { { std::lock_guard<std::mutex> l(m); free.push_back(v); } cv.notify_all(); }
 };
 // result arrays of a batch: page-locked (staramd_pinned_alloc), so that the engine's device-to-host copies are DMA transfers straight into them;
@@ -171,7 +170,7 @@ int staramd_cli_main(int argc, char **argv, const staramd_cli_hooks *hooks, star
     struct LoadLock { int fd = -1; void take() { if (const char *p = getenv("STARAMD_INDEX_LOAD_LOCK")) { fd = open(p, O_CREAT | O_RDWR, 0666); if (fd >= 0 && flock(fd, LOCK_EX) != 0) { close(fd); fd = -1; } } }
                       void drop() { if (fd >= 0) { flock(fd, LOCK_UN); close(fd); fd = -1; } } ~LoadLock() { drop(); } } loadLock;
     loadLock.take();
-    if (!getenv("STARAMD_PAGEABLE_BATCHES")) sah_set_batch_alloc(staramd_pinned_alloc, staramd_pinned_free);      // batch arrays in page-locked memory: the uploads are DMA transfers
+    sah_set_batch_alloc(staramd_pinned_alloc, staramd_pinned_free);      // batch arrays in page-locked memory: the uploads are DMA transfers
     void *h = sah_create((int)flags.rest.size(), flags.rest.data(), err, sizeof(err));
     if (!h) { fprintf(stderr, "\n%s\n", err); return 104; }
     if (sah_tool_done(h)) { sah_destroy(h); return 0; }          // --runMode inputAlignmentsFromBAM: nothing to map
@@ -351,73 +350,7 @@ int staramd_cli_main(int argc, char **argv, const staramd_cli_hooks *hooks, star
             }
         });
         std::vector<std::thread> mappers;
-        // STARAMD_OVERLAP_COPIES=1 (one context per device, no second batch per batch -- merged mates, allele-swapped reads): the mapper keeps TWO batches going -- when the kernels
-        // of batch k are done it begins batch k+1 before the results of k leave the device (staramd_map_begin / _wait / _end, include/star_amd_async.h), so the ~100 MB copy runs
-        // beside kernels.  Measured (profiles/r05_e2e_session8_*): a batch every 46.2 ms instead of 47.7 -- but the copy is a shader ("blit") kernel of the runtime, the persistent
-        // kernels of batch k+1 leave it no CU, and it completes when THEY do: the results of every batch arrive one batch late, the post-map stage and the writer run one
-        // batch behind, and a run of 20 batches ends 40 ms later than with blocking calls.  Worth 3 % on a long run, a loss on a short one: off by default.
-        const bool overlapCopies = nDev == nOwners && !sah_needs_second_batch(h) && getenv("STARAMD_OVERLAP_COPIES") && atoi(getenv("STARAMD_OVERLAP_COPIES")) > 0;
-        for (int d = 0; d < nDev && overlapCopies; d++) mappers.emplace_back([&, d] {
-            auto pushDone = [&](const Msg &m) { { std::lock_guard<std::mutex> l(doneM); done[m.seq] = m; } doneCv.notify_all(); };
-            auto begin = [&](Msg &m) -> bool {            // false: the batch goes down the pipeline unmapped (an error is recorded, or it carries no reads)
-                if (failed.load() || m.n <= 0) { if (failed.load()) m.n = 0; return false; }
-                ResBuf &r = rb[m.slot];
-                if (r.reads.size() < m.b.nReads || r.tr.empty()) r.size(std::max<uint64_t>(m.b.nReads, 1024));
-                if (staramd_map_begin(ctx[d], &m.b)) { fail(std::string("EXITING because of FATAL ERROR in the MI355X engine: ") + staramd_last_error()); m.n = 0; return false; }
-                return true;
-            };
-            Msg cur; bool have = false; double curStart = 0;
-            for (;;) {
-                if (!have) {
-                    if (!parsed.pop(cur)) break;
-                    curStart = plog.now();
-                    StageCpu sc(2);
-                    if (!begin(cur)) { cur.merged = false; plog.add(2, cur.seq, curStart, plog.now()); pushDone(cur); continue; }
-                    have = true;
-                }
-                StageCpu sc(2);
-                auto tm = Clock::now();
-                // the upload of the batch behind it, beside the kernels of this one.  Only with ONE mapper: with several, another mapper may pop the batch that was peeked
-                // here, and this context would keep a stale upload (the blocking loop below has the same guard)
-                uint64_t peekedSeq = ~0ull; bool peeked = false;
-                { Msg pk; if (nDev == 1 && parsed.peek(pk) && pk.n > 0) { (void)staramd_prefetch_batch(ctx[d], &pk.b); peeked = true; peekedSeq = pk.seq; } }
-                int rc = staramd_map_wait(ctx[d]);
-                Msg nx; bool haveNx = false, begunNx = false;
-                ResBuf &r = rb[cur.slot];
-                if (!rc) {
-                    haveNx = parsed.tryPop(nx);
-                    if (peeked && (!haveNx || nx.seq != peekedSeq)) (void)staramd_prefetch_cancel(ctx[d]);      // the batch shown to the engine is not the one that follows: its upload is forgotten
-                    const bool passNx = haveNx && !failed.load() && nx.n > 0;
-                    if (passNx) { ResBuf &rn = rb[nx.slot]; if (rn.reads.size() < nx.b.nReads || rn.tr.empty()) rn.size(std::max<uint64_t>(nx.b.nReads, 1024)); }
-                    rc = staramd_map_end(ctx[d], &r.res, passNx ? &nx.b : nullptr);
-                    if (rc == STARAMD_ERR_RESULT_OVERFLOW) {             // more transcripts than the buffers hold -> grow and ask again (the batch is still in flight)
-                        r.tr.resize(r.res.trCount + r.res.trCount / 4 + 4096); r.ex.resize(r.res.exCount + r.res.exCount / 4 + 4096); r.point();
-                        rc = staramd_map_end(ctx[d], &r.res, passNx ? &nx.b : nullptr);
-                    }
-                    begunNx = passNx && !rc;
-                }
-                if (rc) { fail(std::string("EXITING because of FATAL ERROR in the MI355X engine: ") + staramd_last_error()); cur.n = 0; }
-                else {
-                    float st8[8] = {0}; uint64_t cnt[64] = {0};
-                    const int k = staramd_get_timings(ctx[d], st8, 8); const int kc = staramd_get_counters(ctx[d], cnt, 64);
-                    std::lock_guard<std::mutex> l(statM);
-                    msDeviceAll += r.res.msTotalDevice;
-                    if (timedOn) { rep.deviceBusy[d] += since(tm); rep.deviceMs[d] += r.res.msTotalDevice; for (int i = 0; i < k && i < 8; i++) rep.stageMs[i] += st8[i]; for (int i = 0; i < kc && i < 64; i++) rep.counters[i] += cnt[i]; }
-                }
-                cur.merged = false;
-                if (failed.load()) cur.n = 0;
-                plog.add(2, cur.seq, curStart, plog.now());
-                pushDone(cur);
-                have = false;
-                if (haveNx) {
-                    curStart = plog.now();
-                    if (begunNx) { cur = nx; have = true; }
-                    else if (begin(nx)) { cur = nx; have = true; }       // (it was not handed to staramd_map_end, or that call failed before it began it)
-                    else { nx.merged = false; pushDone(nx); }
-                }
-            }
-        });
-        for (int d = 0; d < nDev && !overlapCopies; d++) mappers.emplace_back([&, d] {
+        for (int d = 0; d < nDev; d++) mappers.emplace_back([&, d] {
             Msg m;
             while (parsed.pop(m)) {
                 int rc = 0;
@@ -440,7 +373,8 @@ int staramd_cli_main(int argc, char **argv, const staramd_cli_hooks *hooks, star
                         }
                         return e;
                     };
-                    // the batch that is next in line (if the reader is ahead, as it normally is) starts its upload now, beside the kernels of this one
+                    // the batch that is next in line (if the reader is ahead, as it normally is) starts its upload now, beside the kernels of this one.  Only with ONE
+                    // mapper: with several, another mapper may pop the batch that was peeked here, and this context would keep a stale upload
                     { Msg nx; if (nDev == 1 && parsed.peek(nx) && nx.n > 0) (void)staramd_prefetch_batch(ctx[d], &nx.b); }
                     rc = mapInto(m.b, rb[m.slot], true);
                     m.merged = false;

@@ -336,7 +336,9 @@ def s11_begin_end(S, pool):
     wA, wB = S.want(orc, A), S.want(orc, B)
     eng.map_begin(A.b)
     rA, rB = S.room(S.n), S.room(S.n)
+    o0 = eng.overlapped_batches()
     eng.map_end(rA, B.b)
+    check(eng.overlapped_batches() == o0 + 1, "map_end(A, next=B): B was not begun beside the copy of A's results (overlapped %d -> %d)" % (o0, eng.overlapped_batches()))
     eng.map_end(rB)
     S.expect("map_end(A, next=B)", rA, wA, S.n)
     S.expect("map_end(B)", rB, wB, S.n)

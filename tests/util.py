@@ -75,6 +75,41 @@ PARAM_SWEEP = {
 }
 
 
+# Rarely taken paths of the engine, forced by shrinking its work space through the STARAMD_* knobs:
+#   tiny pools            -> bump allocators overflow, the host doubles the pool and re-runs the batch
+#   2 windows / 2 blocks  -> every read with more windows goes through the middle k_windows launch (larger table in LDS);
+#                            with a 3-window middle table, on to the last launch (table in global memory); with the
+#                            middle launch off, straight to the last launch
+#   256-byte record arena -> windows re-walked with the record arena in HBM
+#   tiny candidate logs   -> maxScoreMate-sensitive windows re-walked (k_stitch_win mode 1) instead of replayed
+#   every read heavy / every read light -> both kinds of stitch work items
+FORCED = {
+    "tiny_pools": {"STARAMD_POOL_SLACK": "64", "STARAMD_SEEDS_PER_READ": "1", "STARAMD_WINDOWS_PER_READ": "1", "STARAMD_WA_PER_READ": "1", "STARAMD_TR_PER_READ": "1"},
+    "window_overflow": {"STARAMD_CAP_WINDOWS": "2", "STARAMD_CAP_WA_BLOCKS": "2"},
+    "window_overflow_twice": {"STARAMD_CAP_WINDOWS": "1", "STARAMD_CAP_WA_BLOCKS": "1", "STARAMD_CAP_WINDOWS_MID": "3", "STARAMD_CAP_WA_BLOCKS_MID": "3"},
+    "window_overflow_no_middle": {"STARAMD_CAP_WINDOWS": "2", "STARAMD_CAP_WA_BLOCKS": "2", "STARAMD_CAP_WINDOWS_MID": "0"},
+    "arena_overflow": {"STARAMD_STITCH_ARENA": "256"},
+    "log_overflow": {"STARAMD_CAND_KB_PER_WAVE": "1"},
+    "all_heavy": {"STARAMD_LIGHT_EST": "0"},
+    "all_light": {"STARAMD_LIGHT_EST": "4000000000"},
+    "block_overflow": {"STARAMD_CAP_WA_BLOCKS": "2", "STARAMD_CAP_WA_BLOCKS_MID": "3"},      # seed-list blocks run out before table rows do (first and middle launch)
+    "no_pruning": {"STARAMD_PRUNE": "0"},
+    "lane_all_classes": {"STARAMD_LANE_CLASS": "31"},         # every light read of few seeds per window through the lane-per-read stitcher (k_stitch_lane.hip), not only the cheapest classes
+    "lane_off": {"STARAMD_LANE": "0"},                        # ... and none of them: the cooperative walk alone
+    "lean_tiny_lane_off": {"STARAMD_LEAN_DEPTH": "3", "STARAMD_LANE": "0"},
+    "main_depth_tiny": {"STARAMD_MAIN_DEPTH": "3"},           # the main cooperative launch behind the lane kernel holds windows of 2 seeds: almost everything goes on to the full-depth launch
+    "main_depth_off": {"STARAMD_MAIN_DEPTH": "0"},            # one cooperative launch at full depth (three blocks per CU)
+    "lane_tiny_arena": {"STARAMD_LANE_CLASS": "31", "STARAMD_LANE_ARENA": "256"},   # records outgrow the lane's arena: the read goes on to the cooperative kernel
+    "no_sjdb_hash": {"STARAMD_NO_SJDB_HASH": "1"},            # annotated junctions looked up by bisection (what an index does whose coordinates / junction count do not fit the hash)
+    "no_leaf_skipping": {"STARAMD_PRUNE": "3"},               # window pruning as in round 3, every leaf of every walked window finalised
+    "win_owner_map_off": {"STARAMD_WIN_OWNER_MAP": "0"},      # k_windows: the covered bins in a Bloom filter + serial owner look-ups (what a read does whose windows cover more bins than the owner map holds)
+    "win_owner_map_tiny": {"STARAMD_WIN_HASH_BITS": "1024", "STARAMD_WIN_HASH_BITS_MID": "4096"},     # 32-slot owner map: reads switch between the map and the filter
+    "seed_unit_pool_tiny": {"STARAMD_SEED_GROUPS_PER_READ": "1"},   # the group / unit pools hold less than half of the batch: the rest is handed on to k_seed_search
+    "seed_one_slot_per_unit": {"STARAMD_SEED_SLOT_LIMIT": "1"},     # a unit that finds a second seed hands its read on
+    "no_sa_keys": {"STARAMD_SA_KEYS": "0"},                         # the seed stage probes the packed suffix array and the genome (what it does with a sparse suffix array, or when 16 bytes per suffix do not fit)
+}
+
+
 _PREPARED = {}
 
 
