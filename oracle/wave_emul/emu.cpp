@@ -74,9 +74,13 @@ struct Sched {
     bool strictSites = getenv("STARAMD_EMUL_STRICT_SITES") != nullptr;
     unsigned left = 0;
     uint64_t progress = 0, switches = 0, limit = getenv("STARAMD_EMUL_MAX_SWITCHES") ? strtoull(getenv("STARAMD_EMUL_MAX_SWITCHES"), nullptr, 10) : 0;
+    ~Sched() { for (void *p : stacks) munmap(p, STACK_BYTES); if (hashLog) fclose(hashLog); }
 };
 static thread_local Sched *S = nullptr;
-static Sched &sched() { if (!S) S = new Sched(); return *S; }
+// A thread that ends gives its lanes' stacks back: 256 work-items are 512 mappings, and a process whose tests launch from a fresh thread each
+// time (tests/test_bgzf_emul.py::compress_desc) met the kernel's limit of 65530 mappings after 127 such threads.
+static thread_local struct SchedOwner { ~SchedOwner() { delete S; S = nullptr; } } schedOwner;
+static Sched &sched() { if (!S) { S = new Sched(); (void)&schedOwner; } return *S; }
 
 // A lane that has to wait hands over to the next live lane of its wavefront directly; the last one of the pass returns to the scheduler
 // (which looks for progress, other wavefronts, the end of the block).

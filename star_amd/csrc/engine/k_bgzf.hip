@@ -5,9 +5,9 @@
 //   stage      the block into LDS; CRC32 as per-lane partial CRCs over the lane's slice, joined by multiplication with x^(8 * bytes after it) mod P
 //   candidates (level > 0) for every position the latest earlier position with the same 4-byte hash: the block is walked in chunks of 64 or 32
 //              positions, each position reads the hash head of the chunks before its own, then the heads move on by atomicMax (order-independent)
-//   parse      every lane parses its own slice of ceil(n / 256) bytes, matches kept inside the slice: greedy (levels 1-3) or with one step of lazy
-//              evaluation (4-9, -1); tokens overwrite the candidates in the workgroup's global scratch; literal/length and distance
-//              histograms by LDS atomicAdd
+//   parse      every lane parses its own slice of ceil(n / 256) bytes, matches kept inside the slice: greedy on the one candidate (levels 1-3) or the
+//              longest of up to 4 candidates along the chain with one step of lazy evaluation (4-9, -1); tokens into the workgroup's global
+//              scratch beside the candidates; literal/length and distance histograms by LDS atomicAdd
 //   codes      Huffman code lengths (Moffat-Katajainen in place on the frequency-sorted symbols, one lane per tree; limited to 15 / 7 bits by
 //              moving codes down until the Kraft sum is one), canonical codes, the run-length coded tree description
 //   choose     the smallest of dynamic Huffman (BTYPE 2), fixed Huffman (BTYPE 1) and stored (BTYPE 0); stored always fits a slot
@@ -61,7 +61,8 @@ __device__ __forceinline__ uint32_t log2u(uint32_t x) { return 31 - __clz((int)x
 // length 3..258 -> symbol 257..285, extra bits, extra value
 __device__ __forceinline__ uint32_t lenSym(uint32_t L, uint32_t &eb, uint32_t &ev) {
     if (L <= 10) { eb = 0; ev = 0; return 254 + L; }
-    if (L == 258) { eb = 0; ev = 0; return 285; }
+    if (L == 258) { eb = 0; ev = 0; return 285; }         // no block gets here while a lane's slice is at most 255 bytes (0xff00 / 256): lengths stop at 255.
+                                                        // Kept right for whoever raises the slice; covered at routine level (tests/test_bgzf_routines.py)
     uint32_t l = L - 3, e = log2u(l) - 2;
     eb = e; ev = l & ((1u << e) - 1);
     return 257 + 4 * (e + 1) + ((l >> e) & 3);
@@ -187,6 +188,19 @@ __device__ __forceinline__ uint32_t matchLen(const uint8_t *b, uint32_t q, uint3
     return L;
 }
 
+// longest match of position p among its candidates: scr[p] holds (candidate + 1), the candidate's own candidate is the next one back, and so on --
+// a hash chain whose links are at least a chunk long.  Up to `depth` of them within 32768, the nearest of the longest; q1 = (its position + 1)
+__device__ __forceinline__ uint32_t bestMatch(const uint8_t *b, const uint32_t *scr, uint32_t p, uint32_t maxL, uint32_t depth, uint32_t &q1) {
+    uint32_t L = 0, q = scr[p];
+#pragma unroll 1
+    for (uint32_t d = 0; d < depth && q && p - (q - 1) <= 32768; d++) {
+        const uint32_t l = matchLen(b, q - 1, p, maxL);
+        if (l > L) { L = l; q1 = q; if (l == maxL) break; }
+        q = scr[q - 1];
+    }
+    return L;
+}
+
 __device__ void writeHeader(uint8_t *slot, uint32_t total) {
     uint32_t *w = (uint32_t *)slot;
     w[0] = 0x04088b1fu; w[1] = 0; w[2] = 0x0006ff00u; w[3] = 0x00024342u;       // ID1 ID2 CM FLG | MTIME | XFL OS XLEN | 'B' 'C' SLEN
@@ -199,17 +213,19 @@ __device__ void writeTrailer(uint8_t *p, uint32_t crc, uint32_t n) {
 
 }  // namespace
 
-// grid-stride over the blocks; scratch: IN_MAX words per workgroup (candidates, then tokens)
-// level: 0 stored only; 1 candidates in chunks of 64 positions, greedy parse; 2-3 chunks of 32, greedy; 4-9 and -1 chunks of 32, lazy parse
+// grid-stride over the blocks; scratch: 2 * IN_MAX words per workgroup (the candidates, which every lane reads along its chains, and the tokens)
+// level: 0 stored only; 1 candidates in chunks of 64 positions, greedy parse; 2-3 chunks of 32, greedy; 4-9 and -1 chunks of 32, the longest of up to
+// 4 candidates along the chain, lazy parse
 __global__ __launch_bounds__(256) void k_bgzf_blocks(const uint8_t *in, const uint64_t *blkOff, const uint32_t *blkLen, uint32_t nBlocks, int level,
                                                      uint32_t *scratchAll, uint8_t *slots, uint32_t *sizes) {
     __shared__ uint32_t buf[BUF_WORDS];
     __shared__ uint32_t aux[AUX_WORDS];
     uint8_t *lb = (uint8_t *)buf;
     const uint32_t tid = threadIdx.x;
-    uint32_t *scr = scratchAll + (uint64_t)blockIdx.x * IN_MAX;
+    uint32_t *scr = scratchAll + (uint64_t)blockIdx.x * (2 * IN_MAX), *tok = scr + IN_MAX;
     uint32_t *V = aux + A_VAR;
     const bool lazy = level >= 4 || level < 0;
+    const uint32_t DEPTH = lazy ? 4 : 1;
     const uint32_t CHUNK = level == 1 ? 64 : 32;            // positions that look up their candidates between two moves of the hash heads: a
                                                             // candidate is at least as far back as the chunk start, so smaller chunks find nearer matches
 #pragma unroll 1
@@ -253,26 +269,23 @@ __global__ __launch_bounds__(256) void k_bgzf_blocks(const uint8_t *in, const ui
 #pragma unroll 1
             for (uint32_t i = tid; i < A_VAR + 16; i += NT) aux[i] = 0;
             __syncthreads();
-            // ---- parse the lane's slice; tokens (literal: byte; match: len << 16 | dist) overwrite the candidates from the slice start
+            // ---- parse the lane's slice; tokens (literal: byte; match: len << 16 | dist) go to the second half of the scratch, from the slice start
             uint32_t k = 0;
 #pragma unroll 1
             for (uint32_t p = s0; p < s1;) {
-                uint32_t L = 0, q = scr[p];
-                if (q && p - (q - 1) <= 32768) L = matchLen(lb, q - 1, p, min(258u, s1 - p));
-                if (L >= 3 && lazy && L < 32 && p + 1 < s1) {
-                    const uint32_t q2 = scr[p + 1];
-                    if (q2 && p + 1 - (q2 - 1) <= 32768 && matchLen(lb, q2 - 1, p + 1, min(258u, s1 - p - 1)) > L) L = 0;
-                }
+                uint32_t q = 0, q2 = 0;
+                uint32_t L = bestMatch(lb, scr, p, min(258u, s1 - p), DEPTH, q);
+                if (L >= 3 && lazy && L < 32 && p + 1 < s1 && bestMatch(lb, scr, p + 1, min(258u, s1 - p - 1), DEPTH, q2) > L) L = 0;
                 if (L >= 3) {
                     const uint32_t D = p - (q - 1);
                     uint32_t eb, ev;
                     atomicAdd(&aux[A_LITF + lenSym(L, eb, ev)], 1u);
                     atomicAdd(&aux[A_DISTF + distSym(D, eb, ev)], 1u);
-                    scr[s0 + k++] = L << 16 | D;
+                    tok[s0 + k++] = L << 16 | D;
                     p += L;
                 } else {
                     atomicAdd(&aux[A_LITF + lb[p]], 1u);
-                    scr[s0 + k++] = lb[p];
+                    tok[s0 + k++] = lb[p];
                     p++;
                 }
             }
@@ -389,7 +402,7 @@ __global__ __launch_bounds__(256) void k_bgzf_blocks(const uint8_t *in, const ui
                 uint32_t mine = 0;
 #pragma unroll 1
                 for (uint32_t i = 0; i < k; i++) {
-                    const uint32_t t = scr[s0 + i];
+                    const uint32_t t = tok[s0 + i];
                     if (t < 256) { mine += aux[A_LITP + t] >> 16; continue; }
                     uint32_t eb, ev, eb2, ev2;
                     const uint32_t ls = lenSym(t >> 16, eb, ev), ds = distSym(t & 0xffff, eb2, ev2);
@@ -421,7 +434,7 @@ __global__ __launch_bounds__(256) void k_bgzf_blocks(const uint8_t *in, const ui
                 bw.init(buf, hdr + at);
 #pragma unroll 1
                 for (uint32_t i = 0; i < k; i++) {
-                    const uint32_t t = scr[s0 + i];
+                    const uint32_t t = tok[s0 + i];
                     if (t < 256) { const uint32_t cp = aux[A_LITP + t]; bw.put(cp & 0xffff, cp >> 16); continue; }
                     uint32_t eb, ev, eb2, ev2;
                     const uint32_t ls = lenSym(t >> 16, eb, ev), ds = distSym(t & 0xffff, eb2, ev2);
@@ -568,7 +581,7 @@ int staramd_bgzf_create(staramd_bgzf **out, int device, uint64_t initialInputByt
     z->grid = (uint32_t)std::max(1, 2 * prop.multiProcessorCount);          // two 80 KiB workgroups per CU
     if ((e = hipStreamCreate(&z->st)) != hipSuccess) return bad(failHip("hipStreamCreate", e));
     for (auto &x : z->ev) if ((e = hipEventCreate(&x)) != hipSuccess) return bad(failHip("hipEventCreate", e));
-    if ((e = hipMalloc((void **)&z->dScratch, (uint64_t)z->grid * IN_MAX * 4)) != hipSuccess) return bad(failHip("hipMalloc", e));
+    if ((e = hipMalloc((void **)&z->dScratch, (uint64_t)z->grid * IN_MAX * 8)) != hipSuccess) return bad(failHip("hipMalloc", e));
     if (initialInputBytes) {
         const uint64_t nb = (initialInputBytes + IN_MAX - 1) / IN_MAX;
         if (growIn(z, initialInputBytes) || growOut(z, staramd_bgzf_bound(initialInputBytes)) || growBlk(z, nb)) return bad(-1);

@@ -1,6 +1,7 @@
 """Child process of tests/test_gpu_bgzf.py: one GPU step, under the time limit the parent sets.
     bgzf_gpu_run.py lib <vectors.pkl> <out.pkl>                   the vectors through libstaramd.so's compressor, one call each, then from 4 threads at once
-    bgzf_gpu_run.py run <info.pkl> <prefix> Host|Device <batch>   alignReads with capi.Engine, BAM records compressed as the mode says"""
+    bgzf_gpu_run.py run <info.pkl> <prefix> Host|Device <batch>   alignReads with capi.Engine, BAM records compressed as the mode says
+    bgzf_gpu_run.py many <out.pkl>                                test_bgzf_emul.many_calls: one call of more than 3 x as many blocks as workgroups"""
 import os
 import pickle
 import sys
@@ -46,5 +47,16 @@ def run_step(info_path, prefix, mode, batch):
             bz.close()
 
 
+def many_step(out_path):
+    import torch
+    grid = 2 * torch.cuda.get_device_properties(0).multi_processor_count         # staramd_bgzf_create: two workgroups per CU
+    bz = capi.BgzfDevice(device=0)
+    try:
+        res = E.many_calls(bz, grid)
+    finally:
+        bz.close()
+    pickle.dump(res, open(out_path, "wb"))
+
+
 if __name__ == "__main__":
-    {"lib": lib_step, "run": run_step}[sys.argv[1]](*sys.argv[2:])
+    {"lib": lib_step, "run": run_step, "many": many_step}[sys.argv[1]](*sys.argv[2:])

@@ -1,5 +1,6 @@
 """--gpuBAMcompression Device on the MI355X: the shipped compressor (k_bgzf.hip in libstaramd.so) makes the same bytes as the wave emulator's
-build of the same source (tests/test_bgzf_emul.py), alone and from 4 threads at once; whole runs with the BAM records compressed on the device
+build of the same source (tests/test_bgzf_emul.py), alone and from 4 threads at once; a call of three times as many blocks as the kernel has
+workgroups equals its blocks compressed one per call; whole runs with the BAM records compressed on the device
 decompress to exactly what the Host path and the reference write.  Every GPU step is a child process under a time limit of its own."""
 import os
 import pickle
@@ -40,6 +41,17 @@ def test_shipped_library_matches_emulator(tmp_path, built):
                     assert got["threads"][(i, lv, k)] == want, (i, lv, k)
     finally:
         emu.close()
+
+
+def test_more_blocks_than_workgroups(tmp_path, built):
+    """the block loop of a workgroup beyond its first trip (LDS, V[] and the scratch slice left by the block before), and the handle's buffers
+    growing between calls: every member of the large call equals the same content compressed alone, and inflates to it"""
+    op = str(tmp_path / "many.pkl")
+    _child(["many", op], timeout=600)
+    res = pickle.load(open(op, "rb"))
+    print("many: %d workgroups, %d blocks, %.1f MB per call; the large calls took %s s" % (res["grid"], res["nb"], res["bytes"] / 1e6, ", ".join("%.2f" % res[lv][3] for lv in (1, 6, 0))))
+    assert res["grid"] >= 64, "not the workgroup count of a GPU"
+    E.check_many(res)
 
 
 EOF_MARK = E.EOF_MARK
