@@ -179,6 +179,16 @@ __device__ __forceinline__ u8 gcGet(const u8 *G, GCache &c, i64 pos) {
 #define SJ_INFO_SHL(i) (((i) >> 8) & 255u)
 #define SJ_INFO_SHR(i) (((i) >> 16) & 255u)
 __device__ __forceinline__ u32 sjdbHashSlot(u64 start, u32 mask) { return (u32)((start * 0x9E3779B97F4A7C15ull) >> 40) & mask; }
+// host side: the junctions into a zeroed table of mask + 1 slots (engine.hip buildSjdbHash at upload; oracle/stitch_routines_check.cpp fills its tables with the same code)
+static inline void sjdbHashFill(u64 *tab, u32 mask, const u64 *start, const u64 *end, const u8 *motif, const u8 *strand, const u8 *shiftLeft, const u8 *shiftRight, u32 n) {
+    for (u32 i = 0; i < n; i++) {
+        const u64 st = start[i];
+        u32 h = (u32)((st * 0x9E3779B97F4A7C15ull) >> 40) & mask;
+        while (tab[2 * (size_t)h]) h = (h + 1) & mask;
+        tab[2 * (size_t)h] = ((u64)(i + 1) << SJH_START_BITS) | st;
+        tab[2 * (size_t)h + 1] = end[i] | ((u64)SJ_INFO(motif[i] & 7u, strand[i] & 3u, shiftLeft[i], shiftRight[i]) << SJH_START_BITS);
+    }
+}
 // one lane: index of the junction (x, y) or -1
 __device__ __forceinline__ int sjdbHashFind(const u64 *tab_, u32 mask, u64 x, u64 y) {
     const __attribute__((address_space(1))) u64 *tab = GLOBAL(u64, tab_);

@@ -206,13 +206,7 @@ static int buildSjdbHash(staramd_ctx *c, const staramd_genome *g) {
     u32 slots = 128; while (slots < 2u * g->sjdbN) slots <<= 1;
     std::vector<u64> tab((size_t)slots * 2, 0);
     const u32 mask = slots - 1;
-    for (u32 i = 0; i < g->sjdbN; i++) {
-        const u64 st = g->sjdbStart[i];
-        u32 h = (u32)((st * 0x9E3779B97F4A7C15ull) >> 40) & mask;
-        while (tab[2 * (size_t)h]) h = (h + 1) & mask;
-        tab[2 * (size_t)h] = ((u64)(i + 1) << SJH_START_BITS) | st;
-        tab[2 * (size_t)h + 1] = g->sjdbEnd[i] | ((u64)SJ_INFO(g->sjdbMotif[i] & 7u, g->sjdbStrand[i] & 3u, g->sjdbShiftLeft[i], g->sjdbShiftRight[i]) << SJH_START_BITS);
-    }
+    sjdbHashFill(tab.data(), mask, g->sjdbStart, g->sjdbEnd, g->sjdbMotif, g->sjdbStrand, g->sjdbShiftLeft, g->sjdbShiftRight, g->sjdbN);
     int rc = devUpload(c->indexAllocs, &X.sjdbHash, (const u64 *)tab.data(), (u64)slots * 2);
     if (!rc) X.sjdbHashMask = mask;
     return rc;

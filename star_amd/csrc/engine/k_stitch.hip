@@ -130,7 +130,10 @@ __device__ static bool coopExtendChecked(StitchCtx &c, u32 lane, u32 rStart, u64
 // ---- binarySearch2.cpp:3-43: index of the junction (x = start, y = end) in the sorted sjdb arrays, < 0 if absent ----
 // 64-ary search: every round 64 lanes probe 64 evenly spaced starts, the count of "smaller" answers narrows the range
 // 64-fold; then the run of equal starts is compared against y by all lanes at once.  (sjdb junctions are unique
-// (start,end) pairs -- sjdbPrepare collapses duplicates -- so "the" match is well defined.)
+// (start,end) pairs -- sjdbPrepare collapses duplicates -- so "the" match is well defined.  A precondition of this
+// routine, of coopSjdbHash and of sjdbHashFind: with a pair stored twice this one returns the first index, the hash
+// table the one filled first and binarySearch2 whichever its bisection meets; oracle/stitch_routines_check.cpp holds
+// the three against a linear scan on tables of unique pairs only.)
 __device__ static int coopSjdbFind(u32 lane, u64 x, u64 y, const u64 *Xs_, const u64 *Ys_, u32 N) {
     const GLOBAL_AS u64 *Xs = (const GLOBAL_AS u64 *)Xs_, *Ys = (const GLOBAL_AS u64 *)Ys_;
     if (N == 0 || x > Xs[N - 1] || x < Xs[0]) return -1;
@@ -527,6 +530,7 @@ template <bool BIG, class EXP, class HP> __device__ static void recordCandidateI
             for (; base < nW0; base += NLANE) {
                 u32 k = base + lane; bool have = k < nW0;
                 u16 rk = have ? wr.rank[k] : (u16)0;
+                LOCKSTEP();                       // the entries move down by base - outN: a lane's target is the source of a lane below it
                 if (have) wr.rank[outN + lane] = rk;
                 outN += min(NLANE, nW0 - base);
             }
