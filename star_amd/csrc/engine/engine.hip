@@ -1,7 +1,7 @@
 // engine.hip -- C ABI of the MI355X engine (include/star_amd.h): index upload, work-space, launches, timing.
 // The hot path has no CPU fallback: every entry point fails with an error code when the GPU or the
 // kernels are not usable.
-#include "dev.h"
+#include "launch_geom.h"
 #include "../index/hip_backend.h"
 #include "../index/sjdb_core.h"
 #include "../../../include/star_amd_index.h"
@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <climits>
 #include <cmath>
 #include <string>
 #include <vector>
@@ -33,23 +34,20 @@ extern "C" __global__ void k_scan_offsets(DevBatch B, u32 *blockTot, u32 nBlocks
 extern "C" __global__ void k_gather(DevBatch B, const u32 *trBase, const u32 *exBase, const u32 *blockBase, staramd_read_result *outReads,
                                     staramd_transcript *outTr, u32 outTrCap, staramd_exon *outEx, u32 outExCap);
 
-// per-lane / per-wave work-space sizes (same formulas as the kernels)
-static inline u32 waRowsH(u32 capDepth) { return capDepth == 0 ? (u32)WA_MAX : std::min<u32>(capDepth - 1u, (u32)WA_MAX); }
-static inline u32 stitchStateBytesH(u32 capDepth, u32 capRank, u32 arenaBytes) {
-    u32 b = capDepth * 112u + 2u * STARAMD_MAX_N_EXONS * 32u + ((capRank * 2u + 31u) & ~31u) + waRowsH(capDepth) * 32u + 96u + arenaBytes;
-    return (b + 127u) & ~127u;
-}
-static inline u64 winWaveBytesH(u32 capW, u32 capBlocks, u32 big) {
-    u64 b = (u64)capBlocks * WA_MAX * sizeof(DWA);
-    if (big) b += (u64)capW * 8 * sizeof(u32) + 4096 / 8;
-    return (b + 255) & ~255ull;
-}
-
 static thread_local std::string g_err;
 extern "C" const char *staramd_last_error(void) { return g_err.c_str(); }
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { g_err = std::string(#x) + ": " + hipGetErrorString(e_); return STARAMD_ERR_DEVICE; } } while (0)
 
+// events recorded on the compute stream while a batch is enqueued, in the order of enqueueAll: EV_WIN_FIRST behind the first k_windows launch, EV_WIN_TABLES behind the
+// last, EV_WINDOWS behind k_order_*; EV_LANE behind k_stitch_lane, EV_PASS0 behind the cooperative launches of pass 0, EV_STITCH behind k_stitch_finish
+enum { EV_START, EV_SEED, EV_WIN_FIRST, EV_WIN_TABLES, EV_WINDOWS, EV_LANE, EV_PASS0, EV_STITCH, EV_END, EV_N };
+// stage times of the last batch (staramd_get_timings)
+enum { MS_SEED, MS_WIN_TABLES, MS_ORDER, MS_PASS0, MS_REDECIDE, MS_GATHER, MS_TOTAL, MS_WIN_MID_BIG, MS_LANE, MS_N };
+// pinned read-back of a batch, in 32-bit words: the two totals of k_scan_offsets, the cursors, the counters
+enum { HS_TOTALS = 0, HS_CURSORS = 8, HS_COUNTERS = HS_CURSORS + CUR_N, HS_WORDS = 64 + CUR_N };
+// one launch shape of the cooperative stitcher (k_stitch_win, k_stitch_replay): frames of the walk stack, bytes of record arena in LDS, grid
+struct StitchShape { u32 depth = 0, arena = 0, blocks = 0; };
 
 struct staramd_ctx {
     int device = 0;
@@ -59,9 +57,9 @@ struct staramd_ctx {
     std::vector<void *> indexAllocs, workAllocs;
     u32 maxReads = 0; u64 maxBases = 0;
     DevBatch B;
-    u8 *dBases = nullptr; u64 *dReadOffset = nullptr; u16 *dMate1 = nullptr, *dMM = nullptr;
+    const bool verbose = getenv("STARAMD_VERBOSE") != nullptr;      // (knobs are read when the context is made: not on the launch path)
     // two sets of input buffers + a copy stream: the batch that follows is uploaded while this one is on the device (staramd_prefetch_batch, include/star_amd_async.h).
-    // in[k].pending: the set holds an uploaded batch that staramd_map_batch has not consumed yet; cur: the set the last mapped batch used (dBases ... above point into it)
+    // in[k].pending: the set holds an uploaded batch that staramd_map_batch has not consumed yet; cur: the set the last mapped batch used (B.bases ... point into it)
     struct InSet { u8 *bases = nullptr; u64 *readOffset = nullptr; u16 *mate1 = nullptr, *mm = nullptr; hipEvent_t up = nullptr;
                    const uint8_t *hBases = nullptr; const uint64_t *hReadOffset = nullptr; u32 nReads = 0; bool pending = false; } in[2];
     // staramd_map_begin / staramd_map_end (include/star_amd_async.h): a batch whose kernels are enqueued; its flags and totals looked at; the copy of the results of the
@@ -89,14 +87,16 @@ struct staramd_ctx {
     u32 hashBits = 4096, winOwnerMap = 1;         // first launch: bits of the covered-bins filter = 32 x slots of the owner map (k_window.hip)
     // stitch kernel: one lane per read; fast pass (compact arena) + big pass (worst-case arena)
     u32 lightEst = 65536;                 // reads whose walk-size estimate is at most this are ONE stitch work item
-    u32 stBlocks = 0, stBlocksBig = 0, replayBlocks = 0; u8 *scrStitch = nullptr, *scrStitchBig = nullptr;
-    u32 capDepth = 0, capRank = 0, arenaFast = 0, arenaBig = 0, ldsWordsCap = 0;
-    // lean pass-0 launch: windows of at most leanDepth-1 seeds (almost all) walked with a small LDS slice per wavefront, so that more
-    // wavefronts are resident per CU; the others are handed to a second launch with the full-size slice (0 = one full-size launch)
-    u32 leanDepth = 0, leanArena = 0, stBlocksLean = 0;
-    // main cooperative launch behind the lane kernel: a walk stack of mainDepth frames (windows of up to mainDepth - 1 seeds: all but a handful) makes the wavefront's LDS
-    // slice 10 KB instead of 12.5 = a FOURTH block per CU; what holds more seeds goes on to the full-depth launch
-    u32 mainDepth = 0, stBlocksMain = 0;
+    u8 *scrStitchBig = nullptr; u32 capRank = 0, arenaBig = 0;
+    StitchShape stFull;                   // walk stack of seedPerWindowNmax + 1 frames: takes any window
+    // lean pass-0 launch: windows of at most depth - 1 seeds (almost all) walked with a small LDS slice per wavefront, so that more
+    // wavefronts are resident per CU; the others are handed to a second launch with the full-size slice (depth 0 = one full-size launch)
+    StitchShape stLean;
+    // main cooperative launch behind the lane kernel: a walk stack of STARAMD_MAIN_DEPTH = 33 frames (windows of up to 32 seeds: all but a handful) makes the wavefront's LDS
+    // slice 10 KB instead of 12.5 = a FOURTH block per CU; what holds more seeds goes on to the full-depth launch (depth 0 = no such launch)
+    StitchShape stMain;
+    StitchShape stReplay;                 // k_stitch_replay: no walk stack, no read in LDS
+    u32 maxStBlocks = 0;                  // the largest grid of the four: wavefronts that own a record arena in scrStitchBig and a slot of candTops
     // lane-per-read stitcher (k_stitch_lane.hip): takes the light reads whose windows hold few seeds; the cooperative kernel gets the rest
     u32 laneBlocks = 0, laneArenaBytes = 0, laneClass = 3; u8 *scrLane = nullptr;
     u32 prune = 15;                       // STARAMD_PRUNE: bit 0 = window pruning, bit 1 = two-mate windows of a light read first, bit 2 = single-mate leaves of two-mate windows skipped (5.6),
@@ -104,13 +104,13 @@ struct staramd_ctx {
     u32 ldsLimit = 65536;                 // dynamic LDS a block may ask for
     u32 *dTrBase = nullptr, *dExBase = nullptr, *dTotals = nullptr, *dBlockTot = nullptr;
     staramd_read_result *dOutReads = nullptr; staramd_transcript *dOutTr = nullptr; staramd_exon *dOutEx = nullptr;
-    hipEvent_t ev[10];
+    hipEvent_t ev[EV_N] = {};
     hipEvent_t evWait = nullptr;          // blocking-sync event: the mapper thread SLEEPS while its batch is on the device (hipStreamSynchronize spins on a core; the
                                           // front end runs one mapper thread per context beside its parser and formatter threads, on hosts with a CPU quota)
-    float ms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; float ms8 = 0;   // per-stage HIP-event times of the last batch (staramd_get_timings)
+    float ms[MS_N] = {};                  // per-stage HIP-event times of the last batch (staramd_get_timings)
     u64 counters[DC_N];
     u32 residentReads = 0; u32 residentMaxLread = 0;
-    u32 *hostScratch = nullptr;         // pinned: totals + cursors + counters read-back
+    u32 *hostScratch = nullptr;         // pinned: totals + cursors + counters read-back (HS_*)
     std::vector<u64> rebased;           // read offsets of a batch that does not start at base 0
     // a context created with staramd_create_shared maps against the resident index of its OWNER (same device): work space, stream and
     // events are its own, X / dX are copies of the owner's, refreshed whenever the owner's index changes
@@ -137,6 +137,15 @@ template <class T> static int devUpload(std::vector<void *> &reg, const T **dst,
 }
 
 static void freeAll(std::vector<void *> &v) { for (void *p : v) (void)hipFree(p); v.clear(); }
+// one allocation of a registry, freed and forgotten (nothing happens for a pointer the registry does not hold)
+static void devFree(std::vector<void *> &reg, const void *p) {
+    for (size_t i = 0; i < reg.size(); i++) if (reg[i] == p) { (void)hipFree(reg[i]); reg.erase(reg.begin() + i); return; }
+}
+template <class T> static int devRealloc(std::vector<void *> &reg, T **p, u64 n) {
+    devFree(reg, *p);
+    *p = nullptr;
+    return devAlloc(reg, p, n);
+}
 
 // genomic-length score term int(ceil(log2(double(gLen))*scale-0.5)) (stitchWindowAligns.cpp:221-225) as integer
 // break points: evaluated with the host's libm exactly as the reference does, the device only compares integers.
@@ -220,10 +229,7 @@ extern "C" __global__ void k_sak_build(const DevIndex *Xp, u64 *out, u64 n0, u64
 // passes of a 2-pass run cost 6.4 s (profiles/r06_two_pass_leg_*), the rebuild itself 0.46 s
 static void dropSak(staramd_ctx *c, bool keepAllocation = false) {
     DevIndex &X = c->X;
-    if (c->sakBuf && !keepAllocation) {
-        for (size_t i = 0; i < c->indexAllocs.size(); i++) if (c->indexAllocs[i] == (void *)c->sakBuf) { (void)hipFree(c->indexAllocs[i]); c->indexAllocs.erase(c->indexAllocs.begin() + i); break; }
-        c->sakBuf = nullptr; c->sakCapBytes = 0;
-    }
+    if (c->sakBuf && !keepAllocation) { devFree(c->indexAllocs, c->sakBuf); c->sakBuf = nullptr; c->sakCapBytes = 0; }
     X.SAK = nullptr; X.sakBases = 0;
 }
 static int buildSak(staramd_ctx *c) {
@@ -239,7 +245,7 @@ static int buildSak(staramd_ctx *c) {
         if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return 0;
         const u64 reserve = (u64)envU32("STARAMD_SA_KEYS_RESERVE_GB", 48) << 30;
         if ((u64)freeB < need + std::min<u64>(reserve, (u64)totalB / 4)) {
-            if (getenv("STARAMD_VERBOSE")) fprintf(stderr, "staramd: no keys beside the suffix array: %.1f GB needed, %.1f GB free\n", need / 1e9, freeB / 1e9);
+            if (c->verbose) fprintf(stderr, "staramd: no keys beside the suffix array: %.1f GB needed, %.1f GB free\n", need / 1e9, freeB / 1e9);
             return 0;
         }
         // room for the suffixes a junction insertion adds (2 x junctions x sjdbLength: 0.4e9 for a million junctions of 2 x 100 bases), so that the rebuild behind it fits
@@ -259,7 +265,7 @@ static int buildSak(staramd_ctx *c) {
     float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     X.SAK = out; X.sakBases = X.saiNbases;
     HIPCHK(hipMemcpy(c->dX, &X, sizeof(DevIndex), hipMemcpyHostToDevice));
-    if (getenv("STARAMD_VERBOSE")) fprintf(stderr, "staramd: keys beside the suffix array: %.1f GB, built in %.0f ms\n", need / 1e9, ms);
+    if (c->verbose) fprintf(stderr, "staramd: keys beside the suffix array: %.1f GB, built in %.0f ms\n", need / 1e9, ms);
     return 0;
 }
 
@@ -271,7 +277,6 @@ static int uploadIndex(staramd_ctx *c, const staramd_genome *g, const staramd_pa
     if (g->gSAindexNbases > 16 || g->GstrandBit + 3 > 63) { g_err = "unsupported index geometry"; return STARAMD_ERR_ARG; }
     if (p->seedPerWindowNmax > WA_MAX || p->seedPerWindowNmax < 1) { g_err = "seedPerWindowNmax must be in 1..64 on the device (one lane per window seed)"; return STARAMD_ERR_ARG; }
     if (p->alignTranscriptsPerWindowNmax > 2000 || p->alignTranscriptsPerWindowNmax < 1) { g_err = "alignTranscriptsPerWindowNmax must be in 1..2000 on the device"; return STARAMD_ERR_ARG; }
-    if (p->winAnchorMultimapNmax > 64) { /* anchors are enumerated in chunks of 64 loci: any value works */ }
     // genome with padding
     {
         u8 *dG = nullptr;
@@ -293,10 +298,44 @@ static int uploadIndex(staramd_ctx *c, const staramd_genome *g, const staramd_pa
 }
 
 
-template <class T> static int devRealloc(std::vector<void *> &reg, T **p, u64 n) {
-    for (size_t i = 0; i < reg.size(); i++) if (reg[i] == (void *)*p) { (void)hipFree(reg[i]); reg.erase(reg.begin() + i); break; }
-    *p = nullptr;
-    return devAlloc(reg, p, n);
+// the arrays sized by winCap / waCap and by trCap / exCap: allocated at the capacities B holds now (the work space is made, or growPools has raised them)
+static int allocWinPools(staramd_ctx *c) {
+    DevBatch &B = c->B; std::vector<void *> &R = c->workAllocs; int rc;
+    if ((rc = devRealloc(R, &B.winPool, (u64)B.winCap))) return rc;
+    if ((rc = devRealloc(R, &B.waPool, (u64)B.waCap))) return rc;
+    if ((rc = devRealloc(R, &B.wout, (u64)B.winCap))) return rc;
+    if ((rc = devRealloc(R, &B.items, (u64)B.winCap))) return rc;
+    if ((rc = devRealloc(R, &B.itemClass, (u64)B.winCap))) return rc;
+    if ((rc = devRealloc(R, &B.order, (u64)B.winCap + 64))) return rc;
+    if ((rc = devRealloc(R, &B.redoList, (u64)B.winCap))) return rc;
+    if ((rc = devRealloc(R, &B.replayList, (u64)B.winCap))) return rc;
+    if ((rc = devRealloc(R, &B.heavyList, (u64)B.winCap))) return rc;
+    return devRealloc(R, &B.heavyList2, (u64)B.winCap);
+}
+static int allocTrPools(staramd_ctx *c) {
+    DevBatch &B = c->B; std::vector<void *> &R = c->workAllocs; int rc;
+    if ((rc = devRealloc(R, &B.trPool, (u64)B.trCap))) return rc;
+    if ((rc = devRealloc(R, &B.exPool, (u64)B.exCap))) return rc;
+    if ((rc = devRealloc(R, &c->dOutTr, (u64)B.trCap))) return rc;
+    return devRealloc(R, &c->dOutEx, (u64)B.exCap);
+}
+// the kernels of the next launch read their input from set k
+static void useInSet(staramd_ctx *c, int k) {
+    const staramd_ctx::InSet &I = c->in[k];
+    c->cur = k; c->B.bases = I.bases; c->B.readOffset = I.readOffset; c->B.mate1Length = I.mate1; c->B.mmMaxTotal = I.mm;
+}
+
+// dynamic LDS of a block of 4 wavefronts of the cooperative stitcher: per wavefront the packed read and the walk state of the shape
+static size_t stitchLds(const staramd_ctx *c, const StitchShape &s, u32 readBytes) { return 4 * ((size_t)readBytes + stitchStateBytes(s.depth, c->capRank, s.arena)); }
+// the grid of one launch shape: as many blocks per CU as the device holds with the shape's LDS (at most capPerCU), unless the knob says otherwise.  Returns the blocks per CU.
+template <class K> static int planStitch(staramd_ctx *c, StitchShape &s, K kernel, u32 depth, u32 arena, u32 readBytes, int dfltPerCU, int capPerCU, const char *knob,
+                                         const std::string &label, const std::string &tail = "") {
+    s.depth = depth; s.arena = arena;
+    int perCU = dfltPerCU; const size_t lds = stitchLds(c, s, readBytes);
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, 256, lds) != hipSuccess || perCU < 1) perCU = dfltPerCU;
+    s.blocks = (u32)c->nCU * envU32(knob, (u32)std::min(perCU, capPerCU));
+    if (c->verbose) fprintf(stderr, "staramd: %s %d blocks/CU (LDS %zu B/block)%s\n", label.c_str(), perCU, lds, tail.c_str());
+    return perCU;
 }
 
 static int allocWork(staramd_ctx *c) {
@@ -304,21 +343,18 @@ static int allocWork(staramd_ctx *c) {
     u32 N = c->maxReads; int rc;
     hipDeviceProp_t prop; memset(&prop, 0, sizeof(prop));
     if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) c->nCU = prop.multiProcessorCount;
-    // 64 bytes of padding either side: the seed search compares 8 bases per step and may read a few bytes past a read
-    { u8 *raw = nullptr; if ((rc = devAlloc(R, &raw, c->maxBases + 192))) return rc; if (hipMemset(raw, 4, c->maxBases + 192) != hipSuccess) { g_err = "hipMemset failed"; return STARAMD_ERR_DEVICE; } c->dBases = raw + 64; }
-    if ((rc = devAlloc(R, &c->dReadOffset, (u64)N + 1))) return rc;
-    if ((rc = devAlloc(R, &c->dMate1, (u64)N))) return rc;
-    if ((rc = devAlloc(R, &c->dMM, (u64)N))) return rc;
-    c->in[0].bases = c->dBases; c->in[0].readOffset = c->dReadOffset; c->in[0].mate1 = c->dMate1; c->in[0].mm = c->dMM; c->cur = 0;
-    { u8 *raw = nullptr; if ((rc = devAlloc(R, &raw, c->maxBases + 192))) return rc; if (hipMemset(raw, 4, c->maxBases + 192) != hipSuccess) { g_err = "hipMemset failed"; return STARAMD_ERR_DEVICE; } c->in[1].bases = raw + 64; }
-    if ((rc = devAlloc(R, &c->in[1].readOffset, (u64)N + 1))) return rc;
-    if ((rc = devAlloc(R, &c->in[1].mate1, (u64)N))) return rc;
-    if ((rc = devAlloc(R, &c->in[1].mm, (u64)N))) return rc;
+    for (staramd_ctx::InSet &I : c->in) {
+        // 64 bytes of padding either side: the seed search compares 8 bases per step and may read a few bytes past a read
+        u8 *raw = nullptr; if ((rc = devAlloc(R, &raw, c->maxBases + 192))) return rc; if (hipMemset(raw, 4, c->maxBases + 192) != hipSuccess) { g_err = "hipMemset failed"; return STARAMD_ERR_DEVICE; } I.bases = raw + 64;
+        if ((rc = devAlloc(R, &I.readOffset, (u64)N + 1))) return rc;
+        if ((rc = devAlloc(R, &I.mate1, (u64)N))) return rc;
+        if ((rc = devAlloc(R, &I.mm, (u64)N))) return rc;
+        if (hipEventCreateWithFlags(&I.up, hipEventDisableTiming) != hipSuccess) { g_err = "hipEventCreate failed"; return STARAMD_ERR_DEVICE; }
+    }
     if (hipStreamCreate(&c->copyStream) != hipSuccess) { g_err = "hipStreamCreate failed"; return STARAMD_ERR_DEVICE; }
-    for (int k = 0; k < 2; k++) if (hipEventCreateWithFlags(&c->in[k].up, hipEventDisableTiming) != hipSuccess) { g_err = "hipEventCreate failed"; return STARAMD_ERR_DEVICE; }
     c->packWordsCap = 0;
     DevBatch &B = c->B; memset(&B, 0, sizeof(B));
-    B.bases = c->dBases; B.readOffset = c->dReadOffset; B.mate1Length = c->dMate1; B.mmMaxTotal = c->dMM;
+    useInSet(c, 0);
     if ((rc = devAlloc(R, &B.reads, (u64)N))) return rc;
     const u64 slack = envU32("STARAMD_POOL_SLACK", 65536);
     B.seedCap = (u32)std::min<u64>((u64)N * envU32("STARAMD_SEEDS_PER_READ", 32) + slack, 0xFFFFFFF0ull);
@@ -327,18 +363,8 @@ static int allocWork(staramd_ctx *c) {
     B.trCap = (u32)std::min<u64>((u64)N * envU32("STARAMD_TR_PER_READ", 48) + slack, 0xFFFFFFF0ull);
     B.exCap = (u32)std::min<u64>((u64)B.trCap * 3, 0xFFFFFFF0ull);
     if ((rc = devAlloc(R, &B.seedPool, (u64)B.seedCap))) return rc;
-    if ((rc = devAlloc(R, &B.winPool, (u64)B.winCap))) return rc;
-    if ((rc = devAlloc(R, &B.waPool, (u64)B.waCap))) return rc;
-    if ((rc = devAlloc(R, &B.wout, (u64)B.winCap))) return rc;
-    if ((rc = devAlloc(R, &B.items, (u64)B.winCap))) return rc;
-    if ((rc = devAlloc(R, &B.itemClass, (u64)B.winCap))) return rc;
-    if ((rc = devAlloc(R, &B.order, (u64)B.winCap + 64))) return rc;
-    if ((rc = devAlloc(R, &B.redoList, (u64)B.winCap))) return rc;
-    if ((rc = devAlloc(R, &B.replayList, (u64)B.winCap))) return rc;
-    if ((rc = devAlloc(R, &B.heavyList, (u64)B.winCap))) return rc;
-    if ((rc = devAlloc(R, &B.heavyList2, (u64)B.winCap))) return rc;
-    if ((rc = devAlloc(R, &B.trPool, (u64)B.trCap))) return rc;
-    if ((rc = devAlloc(R, &B.exPool, (u64)B.exCap))) return rc;
+    if ((rc = allocWinPools(c))) return rc;
+    if ((rc = allocTrPools(c))) return rc;
     if ((rc = devAlloc(R, &B.costHist, (u64)64))) return rc;
     if ((rc = devAlloc(R, &B.ovfWin, (u64)N))) return rc;
     if ((rc = devAlloc(R, &B.ovfWin2, (u64)N))) return rc;
@@ -349,9 +375,7 @@ static int allocWork(staramd_ctx *c) {
     if ((rc = devAlloc(R, &c->dTotals, (u64)4))) return rc;
     if ((rc = devAlloc(R, &c->dBlockTot, (u64)2 * ((N + 255) / 256) + 2))) return rc;
     if ((rc = devAlloc(R, &c->dOutReads, (u64)N))) return rc;
-    if ((rc = devAlloc(R, &c->dOutTr, (u64)B.trCap))) return rc;
-    if ((rc = devAlloc(R, &c->dOutEx, (u64)B.exCap))) return rc;
-    if (hipHostMalloc((void **)&c->hostScratch, (64 + CUR_N) * sizeof(u32) + DC_N * sizeof(u64)) != hipSuccess) { g_err = "hipHostMalloc failed"; return STARAMD_ERR_DEVICE; }
+    if (hipHostMalloc((void **)&c->hostScratch, HS_WORDS * sizeof(u32) + DC_N * sizeof(u64)) != hipSuccess) { g_err = "hipHostMalloc failed"; return STARAMD_ERR_DEVICE; }
     const staramd_params &P = c->X.P;
     // ---- seed stage: a lane per unit of the search schedule (k_seed_plan / k_seed_units / k_seed_merge).  2x101 has 12 groups / 10 units per pair, 2x150 16 / 14; a read
     // that does not fit what is left of the pools takes k_seed_search (no regrowth, no re-run): at most 64 blocks, each lane with a PC table sized by seedPerReadNmax
@@ -382,84 +406,98 @@ static int allocWork(staramd_ctx *c) {
     int winPerCU = 3;
     c->winOwnerMap = envU32("STARAMD_WIN_OWNER_MAP", 1);
     { u32 hb = envU32("STARAMD_WIN_HASH_BITS", c->winOwnerMap ? 16384 : 4096); c->hashBits = 1024; while (c->hashBits < hb && c->hashBits < (1u << 18)) c->hashBits <<= 1; }      // a power of two
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&winPerCU, k_windows, 256, 4 * (c->capW * 8 + c->hashBits / 32) * sizeof(u32)) != hipSuccess || winPerCU < 1) winPerCU = 3;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&winPerCU, k_windows, 256, 4 * winLdsWords(c->capW, c->hashBits) * sizeof(u32)) != hipSuccess || winPerCU < 1) winPerCU = 3;
     c->winBlocks = (u32)c->nCU * envU32("STARAMD_WIN_BLOCKS_PER_CU", (u32)winPerCU);
     c->winBlocks = std::max<u32>(1, std::min<u32>(c->winBlocks, (N + 3) / 4));
-    if ((rc = devAlloc(R, &c->scrWin, (u64)c->winBlocks * 4 * winWaveBytesH(c->capW, c->capBlocks, 0)))) return rc;
+    if ((rc = devAlloc(R, &c->scrWin, (u64)c->winBlocks * 4 * winWaveBytes(c->capW, c->capBlocks, 0)))) return rc;
     c->capWMid = envU32("STARAMD_CAP_WINDOWS_MID", 1024); c->capBlocksMid = envU32("STARAMD_CAP_WA_BLOCKS_MID", 1024);
     if (c->capWMid <= c->capW || c->capWMid >= P.alignWindowsPerReadNmax) c->capWMid = 0;
     if (c->capWMid) {
         u32 hb = envU32("STARAMD_WIN_HASH_BITS_MID", c->winOwnerMap ? 262144 : 65536);
         c->hashBitsMid = 4096; while (c->hashBitsMid < hb && c->hashBitsMid < (1u << 18)) c->hashBitsMid <<= 1;       // a power of two
-        while (c->hashBitsMid > 4096 && ((u64)c->capWMid * 8 + c->hashBitsMid / 32) * 4 > 65536) c->hashBitsMid >>= 1;   // table + map within 64 KB of dynamic LDS
-        if (((u64)c->capWMid * 8 + c->hashBitsMid / 32) * 4 > 65536) c->capWMid = (65536 / 4 - c->hashBitsMid / 32) / 8;
+        // table + map within 64 KB of dynamic LDS: a smaller map first, then fewer rows
+        while (c->hashBitsMid > 4096 && (u64)winLdsWords(c->capWMid, c->hashBitsMid) * 4 > 65536) c->hashBitsMid >>= 1;
+        while ((u64)winLdsWords(c->capWMid, c->hashBitsMid) * 4 > 65536) c->capWMid--;
         c->winBlocksMid = envU32("STARAMD_WIN_BLOCKS_MID", (u32)c->nCU * 4u);
-        if ((rc = devAlloc(R, &c->scrWinMid, (u64)c->winBlocksMid * winWaveBytesH(c->capWMid, c->capBlocksMid, 0)))) return rc;
+        if ((rc = devAlloc(R, &c->scrWinMid, (u64)c->winBlocksMid * winWaveBytes(c->capWMid, c->capBlocksMid, 0)))) return rc;
     }
     c->capWBig = P.alignWindowsPerReadNmax; c->capBlocksBig = P.alignWindowsPerReadNmax;
     c->winBlocksBig = envU32("STARAMD_WIN_BLOCKS_BIG", 64);
-    if ((rc = devAlloc(R, &c->scrWinBig, (u64)c->winBlocksBig * 4 * winWaveBytesH(c->capWBig, c->capBlocksBig, 1)))) return rc;
-    // ---- stitch kernel
-    c->capDepth = P.seedPerWindowNmax + 1; c->capRank = P.alignTranscriptsPerWindowNmax + 1;
-    c->arenaFast = envU32("STARAMD_STITCH_ARENA", 6144) & ~31u;
-    c->arenaBig = 2u * (P.alignTranscriptsPerWindowNmax + 2) * (96u + 32u * STARAMD_MAX_N_EXONS);      // twice the largest live set
+    if ((rc = devAlloc(R, &c->scrWinBig, (u64)c->winBlocksBig * 4 * winWaveBytes(c->capWBig, c->capBlocksBig, 1)))) return rc;
+    // ---- stitch kernel: one wavefront per window, walk state in LDS; blocks of 4 wavefronts; one worst-case record arena per wavefront in HBM
+    const u32 capDepth = P.seedPerWindowNmax + 1; c->capRank = P.alignTranscriptsPerWindowNmax + 1;
+    c->arenaBig = 2u * (P.alignTranscriptsPerWindowNmax + 2) * (REC_HDR_BYTES + 32u * STARAMD_MAX_N_EXONS);      // twice the largest live set
     if (c->arenaBig > 2000000u) { g_err = "alignTranscriptsPerWindowNmax too large for the device record arena"; return STARAMD_ERR_ARG; }
-    // one wavefront per window, walk state in LDS; blocks of 4 wavefronts; one worst-case record arena per wavefront in HBM
-    c->arenaFast = envU32("STARAMD_STITCH_ARENA", 3584) & ~31u;
-    int stPerCU = 2;
-    size_t ldsFast = 4 * (size_t)(stitchStateBytesH(c->capDepth, c->capRank, c->arenaFast) + 27 * 4 + 16);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&stPerCU, k_stitch_win, 256, ldsFast) != hipSuccess || stPerCU < 1) stPerCU = 2;
-    c->stBlocks = (u32)c->nCU * envU32("STARAMD_STITCH_BLOCKS_PER_CU", (u32)stPerCU);
-    if (getenv("STARAMD_VERBOSE")) fprintf(stderr, "staramd: k_stitch_win %d blocks/CU (LDS %zu B/block), k_windows %d blocks/CU, k_seed_search %d blocks/CU\n", stPerCU, ldsFast, winPerCU, seedPerCU);
-    // the replay kernel needs no walk stack and no read in LDS: more blocks per CU hide the latency of its candidate-log reads
-    {
-        int rpPerCU = stPerCU;
-        size_t ldsReplay = 4 * (size_t)stitchStateBytesH(0, c->capRank, c->arenaFast);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&rpPerCU, k_stitch_replay, 256, ldsReplay) != hipSuccess || rpPerCU < 1) rpPerCU = stPerCU;
-        c->replayBlocks = (u32)c->nCU * envU32("STARAMD_REPLAY_BLOCKS_PER_CU", (u32)std::min(rpPerCU, 8));
-        if (getenv("STARAMD_VERBOSE")) fprintf(stderr, "staramd: k_stitch_replay %d blocks/CU (LDS %zu B/block)\n", rpPerCU, ldsReplay);
-    }
-    // lean launch geometry (used when the lane kernel is off or does not fit: with the lane kernel in front a lean middle launch -- 20 frames, 7.6 KB per wavefront, 5 wavefronts
+    const u32 arenaFast = envU32("STARAMD_STITCH_ARENA", 3584) & ~31u, nominal = STITCH_READ_BYTES_NOMINAL;
+    const int stPerCU = planStitch(c, c->stFull, k_stitch_win, capDepth, arenaFast, nominal, 2, INT_MAX, "STARAMD_STITCH_BLOCKS_PER_CU", "k_stitch_win",
+                                   ", k_windows " + std::to_string(winPerCU) + " blocks/CU, k_seed_search " + std::to_string(seedPerCU) + " blocks/CU");
+    // the replay kernel needs no walk stack and no read in LDS: more blocks per CU (8 at the most) hide the latency of its candidate-log reads
+    planStitch(c, c->stReplay, k_stitch_replay, 0, arenaFast, 0, stPerCU, 8, "STARAMD_REPLAY_BLOCKS_PER_CU", "k_stitch_replay");
+    // with the lane kernel in front: main launch + full-depth launch
+    u32 mainDepth = envU32("STARAMD_MAIN_DEPTH", 33);
+    if (mainDepth < 3 || mainDepth >= capDepth) mainDepth = 0;
+    if (mainDepth) planStitch(c, c->stMain, k_stitch_win, mainDepth, arenaFast, nominal, stPerCU, INT_MAX, "STARAMD_MAIN_BLOCKS_PER_CU", "k_stitch_win main launch: depth " + std::to_string(mainDepth) + ",");
+    // lean launch (used when the lane kernel is off or does not fit: with the lane kernel in front a lean middle launch -- 20 frames, 7.6 KB per wavefront, 5 wavefronts
     // per SIMD -- was measured and removed in round 5: stitch stage 24.6 ms against 22.7, profiles/r05_ab_session1_*.txt)
-    c->leanDepth = envU32("STARAMD_LEAN_DEPTH", 9); c->leanArena = envU32("STARAMD_LEAN_ARENA", 2048) & ~31u;
-    if (c->leanDepth >= c->capDepth) c->leanDepth = 0;
-    c->mainDepth = envU32("STARAMD_MAIN_DEPTH", 33);
-    if (c->mainDepth < 3 || c->mainDepth >= c->capDepth) c->mainDepth = 0;
-    if (c->mainDepth) {
-        int mpCU = stPerCU;
-        size_t ldsMain = 4 * (size_t)(stitchStateBytesH(c->mainDepth, c->capRank, c->arenaFast) + 27 * 4 + 16);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&mpCU, k_stitch_win, 256, ldsMain) != hipSuccess || mpCU < 1) mpCU = stPerCU;
-        c->stBlocksMain = (u32)c->nCU * envU32("STARAMD_MAIN_BLOCKS_PER_CU", (u32)mpCU);
-        if (getenv("STARAMD_VERBOSE")) fprintf(stderr, "staramd: k_stitch_win main launch: depth %u, %d blocks/CU (LDS %zu B/block)\n", c->mainDepth, mpCU, ldsMain);
-    }
-    c->stBlocksLean = 0;
-    if (c->leanDepth) {
-        int lpCU = stPerCU;
-        size_t ldsLean = 4 * (size_t)(stitchStateBytesH(c->leanDepth, c->capRank, c->leanArena) + 27 * 4 + 16);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&lpCU, k_stitch_win, 256, ldsLean) != hipSuccess || lpCU < 1) lpCU = stPerCU;
-        c->stBlocksLean = (u32)c->nCU * envU32("STARAMD_LEAN_BLOCKS_PER_CU", (u32)lpCU);
-        if (getenv("STARAMD_VERBOSE")) fprintf(stderr, "staramd: k_stitch_win lean launch: depth %u, arena %u B, %d blocks/CU (LDS %zu B/block)\n", c->leanDepth, c->leanArena, lpCU, ldsLean);
-    }
+    u32 leanDepth = envU32("STARAMD_LEAN_DEPTH", 9); const u32 leanArena = envU32("STARAMD_LEAN_ARENA", 2048) & ~31u;
+    if (leanDepth >= capDepth) leanDepth = 0;
+    if (leanDepth) planStitch(c, c->stLean, k_stitch_win, leanDepth, leanArena, nominal, stPerCU, INT_MAX, "STARAMD_LEAN_BLOCKS_PER_CU",
+                              "k_stitch_win lean launch: depth " + std::to_string(leanDepth) + ", arena " + std::to_string(leanArena) + " B,");
     // lane-per-read launch: 256 lanes per block, each with an LDS slot for its packed read and a record arena in HBM
     c->laneBlocks = 0;
     if (envU32("STARAMD_LANE", 1)) {
         int lnPerCU = 4;
-        const size_t ldsLane = 256 * (size_t)(27 * 4);
+        const size_t ldsLane = 256 * (size_t)STITCH_READ_WORDS_NOMINAL * 4;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&lnPerCU, k_stitch_lane, 256, ldsLane) != hipSuccess || lnPerCU < 1) lnPerCU = 2;
         c->laneBlocks = (u32)c->nCU * envU32("STARAMD_LANE_BLOCKS_PER_CU", (u32)lnPerCU);
         c->laneBlocks = std::max<u32>(1, std::min<u32>(c->laneBlocks, (N + 255) / 256));
         c->laneArenaBytes = envU32("STARAMD_LANE_ARENA", 2048) & ~31u;
         if ((rc = devAlloc(R, &c->scrLane, (u64)c->laneBlocks * 256 * c->laneArenaBytes))) return rc;
-        if (getenv("STARAMD_VERBOSE")) fprintf(stderr, "staramd: k_stitch_lane %d blocks/CU (LDS %zu B/block), %u blocks, %u B of record arena per lane\n", lnPerCU, ldsLane, c->laneBlocks, c->laneArenaBytes);
+        if (c->verbose) fprintf(stderr, "staramd: k_stitch_lane %d blocks/CU (LDS %zu B/block), %u blocks, %u B of record arena per lane\n", lnPerCU, ldsLane, c->laneBlocks, c->laneArenaBytes);
     }
-    const u32 maxStBlocks = std::max(std::max(std::max(c->stBlocks, c->stBlocksMain), c->stBlocksLean), c->replayBlocks);
-    if ((rc = devAlloc(R, &c->scrStitchBig, (u64)maxStBlocks * 4 * c->arenaBig))) return rc;
+    const u32 walkBlocks = std::max(std::max(c->stFull.blocks, c->stMain.blocks), c->stLean.blocks);      // the launches that write candidate logs
+    c->maxStBlocks = std::max(walkBlocks, c->stReplay.blocks);
+    if ((rc = devAlloc(R, &c->scrStitchBig, (u64)c->maxStBlocks * 4 * c->arenaBig))) return rc;
     // candidate logs: one private region per wavefront; sized so that a wavefront's share of a full batch fits
     B.candWaveBytes = ((u64)envU32("STARAMD_CAND_KB_PER_WAVE", 0) * 1024) & ~31ull;
-    if (B.candWaveBytes == 0) { u64 per = (u64)N * 6144 / ((u64)c->stBlocks * 4) + 262144; B.candWaveBytes = std::min<u64>(per, 0xFFFF0000ull) & ~31ull; }
-    if ((rc = devAlloc(R, &B.candPool, (u64)std::max(std::max(c->stBlocks, c->stBlocksMain), c->stBlocksLean) * 4 * B.candWaveBytes))) return rc;
-    if ((rc = devAlloc(R, &B.candTops, (u64)maxStBlocks * 4 + 64))) return rc;
+    if (B.candWaveBytes == 0) { u64 per = (u64)N * 6144 / ((u64)c->stFull.blocks * 4) + 262144; B.candWaveBytes = std::min<u64>(per, 0xFFFF0000ull) & ~31ull; }
+    if ((rc = devAlloc(R, &B.candPool, (u64)walkBlocks * 4 * B.candWaveBytes))) return rc;
+    if ((rc = devAlloc(R, &B.candTops, (u64)c->maxStBlocks * 4 + 64))) return rc;
     return 0;
+}
+
+// everything a context owns, released: staramd_destroy, and a create that failed half way
+static void teardown(staramd_ctx *c) {
+    if (c->owner) { auto &v = c->owner->sharers; for (size_t i = 0; i < v.size(); i++) if (v[i] == c) { v.erase(v.begin() + i); break; } }
+    for (staramd_ctx *s : c->sharers) s->owner = nullptr;         // (their index is gone with this context: destroy the sharers first)
+    if (!c->owner) freeAll(c->indexAllocs);
+    freeAll(c->workAllocs);
+    for (hipEvent_t e : c->ev) if (e) (void)hipEventDestroy(e);
+    if (c->evWait) (void)hipEventDestroy(c->evWait);
+    if (c->evDownload) (void)hipEventDestroy(c->evDownload);
+    for (int k = 0; k < 2; k++) if (c->in[k].up) (void)hipEventDestroy(c->in[k].up);
+    if (c->copyStream) (void)hipStreamDestroy(c->copyStream);
+    if (c->hostScratch) (void)hipHostFree(c->hostScratch);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
+}
+// the half of a context that is its own whether it owns its index or shares one: work space, streams, events.  Takes c over: handed out, or torn down.
+static int finishCreate(staramd_ctx *c, int rc, staramd_ctx **out) {
+    if (!rc) rc = allocWork(c);
+    if (!rc) { if (hipStreamCreate(&c->stream) != hipSuccess) { g_err = "hipStreamCreate failed"; rc = STARAMD_ERR_DEVICE; } }
+    if (!rc) for (hipEvent_t &e : c->ev) if (hipEventCreate(&e) != hipSuccess) { g_err = "hipEventCreate failed"; rc = STARAMD_ERR_DEVICE; }
+    if (!rc && hipEventCreateWithFlags(&c->evWait, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) c->evWait = nullptr;
+    if (!rc && hipEventCreateWithFlags(&c->evDownload, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { g_err = "hipEventCreate failed"; rc = STARAMD_ERR_DEVICE; }
+    if (rc) { teardown(c); return rc; }
+    memset(c->counters, 0, sizeof(c->counters));
+    if (c->owner) c->owner->sharers.push_back(c);
+    *out = c;
+    return STARAMD_OK;
+}
+static staramd_ctx *newCtx(int device, uint32_t maxBatchReads, uint64_t maxBatchBases) {
+    staramd_ctx *c = new staramd_ctx();
+    c->device = device; c->maxReads = maxBatchReads; c->maxBases = maxBatchBases ? maxBatchBases : (u64)maxBatchReads * (STARAMD_READ_LEN_MAX + 1);
+    return c;
 }
 
 extern "C" int staramd_create(staramd_ctx **out, int device, const staramd_genome *g, const staramd_params *p, uint32_t maxBatchReads, uint64_t maxBatchBases) {
@@ -467,37 +505,17 @@ extern "C" int staramd_create(staramd_ctx **out, int device, const staramd_genom
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || nDev == 0) { g_err = "no HIP device visible: the seed-search-and-stitch engine needs an MI355X (no CPU fallback)"; return STARAMD_ERR_DEVICE; }
     HIPCHK(hipSetDevice(device));
-    staramd_ctx *c = new staramd_ctx();
-    c->device = device; c->maxReads = maxBatchReads; c->maxBases = maxBatchBases ? maxBatchBases : (u64)maxBatchReads * (STARAMD_READ_LEN_MAX + 1);
-    int rc = uploadIndex(c, g, p);
-    if (!rc) rc = allocWork(c);
-    if (!rc) { if (hipStreamCreate(&c->stream) != hipSuccess) { g_err = "hipStreamCreate failed"; rc = STARAMD_ERR_DEVICE; } }
-    if (!rc) for (int i = 0; i < 10; i++) if (hipEventCreate(&c->ev[i]) != hipSuccess) { g_err = "hipEventCreate failed"; rc = STARAMD_ERR_DEVICE; }
-    if (!rc && hipEventCreateWithFlags(&c->evWait, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) c->evWait = nullptr;
-    if (!rc && hipEventCreateWithFlags(&c->evDownload, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { g_err = "hipEventCreate failed"; rc = STARAMD_ERR_DEVICE; }
-    if (rc) { freeAll(c->indexAllocs); freeAll(c->workAllocs); delete c; return rc; }
-    memset(c->counters, 0, sizeof(c->counters));
-    *out = c;
-    return STARAMD_OK;
+    staramd_ctx *c = newCtx(device, maxBatchReads, maxBatchBases);
+    return finishCreate(c, uploadIndex(c, g, p), out);
 }
 
 extern "C" int staramd_create_shared(staramd_ctx **out, staramd_ctx *owner, uint32_t maxBatchReads, uint64_t maxBatchBases) {
     if (!out || !owner || maxBatchReads == 0) { g_err = "bad arguments"; return STARAMD_ERR_ARG; }
     if (owner->owner) owner = owner->owner;
     HIPCHK(hipSetDevice(owner->device));
-    staramd_ctx *c = new staramd_ctx();
-    c->device = owner->device; c->maxReads = maxBatchReads; c->maxBases = maxBatchBases ? maxBatchBases : (u64)maxBatchReads * (STARAMD_READ_LEN_MAX + 1);
+    staramd_ctx *c = newCtx(owner->device, maxBatchReads, maxBatchBases);
     c->owner = owner; c->X = owner->X; c->dX = owner->dX;
-    int rc = allocWork(c);
-    if (!rc) { if (hipStreamCreate(&c->stream) != hipSuccess) { g_err = "hipStreamCreate failed"; rc = STARAMD_ERR_DEVICE; } }
-    if (!rc) for (int i = 0; i < 10; i++) if (hipEventCreate(&c->ev[i]) != hipSuccess) { g_err = "hipEventCreate failed"; rc = STARAMD_ERR_DEVICE; }
-    if (!rc && hipEventCreateWithFlags(&c->evWait, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) c->evWait = nullptr;
-    if (!rc && hipEventCreateWithFlags(&c->evDownload, hipEventBlockingSync | hipEventDisableTiming) != hipSuccess) { g_err = "hipEventCreate failed"; rc = STARAMD_ERR_DEVICE; }
-    if (rc) { freeAll(c->workAllocs); delete c; return rc; }
-    memset(c->counters, 0, sizeof(c->counters));
-    owner->sharers.push_back(c);
-    *out = c;
-    return STARAMD_OK;
+    return finishCreate(c, 0, out);
 }
 
 // page-locked host memory for the caller's batch / result arrays (include/star_amd.h: the copies of staramd_map_batch then run as DMA
@@ -519,10 +537,6 @@ extern "C" int staramd_update_index(staramd_ctx *c, const staramd_genome *g, con
 
 
 // ---- junction insertion into the resident index (include/star_amd.h) ---------------------------------------------------------------
-static void dropAlloc(std::vector<void *> &reg, const void *p) {
-    for (size_t i = 0; i < reg.size(); i++) if (reg[i] == p) { (void)hipFree(reg[i]); reg.erase(reg.begin() + i); return; }
-}
-
 extern "C" int staramd_insert_junctions(staramd_ctx *c, const staramd_sjdb_args *a, uint8_t *SAout, uint64_t saOutCapacity, uint8_t *SAiOut, uint64_t saiOutCapacity,
                                         staramd_sjdb_result *res) {
     if (!c || !a || !res || !a->Gsj || !a->isOld || (a->oldSjdbN && !a->oldSJind)) { g_err = "staramd_insert_junctions: null argument"; return STARAMD_ERR_ARG; }
@@ -558,7 +572,7 @@ extern "C" int staramd_insert_junctions(staramd_ctx *c, const staramd_sjdb_args 
     if (be.tmp) (void)hipFree(be.tmp);
     if (rc) { if (R.dSApacked) (void)hipFree(R.dSApacked); if (R.dGnew) (void)hipFree(R.dGnew); if (R.dSAiPacked) (void)hipFree(R.dSAiPacked); (void)buildSak(c); refreshSharers(c); return rc; }
     // the new arrays take the place of the old ones
-    dropAlloc(c->indexAllocs, X.G - GPAD); dropAlloc(c->indexAllocs, X.SA); dropAlloc(c->indexAllocs, X.SAi);
+    devFree(c->indexAllocs, X.G - GPAD); devFree(c->indexAllocs, X.SA); devFree(c->indexAllocs, X.SAi);
     c->indexAllocs.push_back(R.dGnew); c->indexAllocs.push_back(R.dSApacked); c->indexAllocs.push_back(R.dSAiPacked);
     X.G = R.dGnew + GPAD; X.SA = R.dSApacked; X.SAi = R.dSAiPacked;
     X.nGenome = R.nGenomeNew; X.nSA = R.nSAnew;
@@ -584,7 +598,7 @@ extern "C" int staramd_insert_junctions_fits(staramd_ctx *c, uint64_t maxJunctio
              + 2 * nGnew + nSAnew * 8ull + nSAi * 8ull                          // SAindex rebuild
              + (2ull << 30);                                                    // sort temporaries, slack
     if (const char *e = getenv("STARAMD_SJDB_FITS_FREE_GB")) freeB = (size_t)(strtod(e, nullptr) * 1e9);      // (tests: pretend this much is free)
-    if (getenv("STARAMD_VERBOSE")) fprintf(stderr, "staramd: resident junction insertion needs up to %.1f GB, %.1f GB free\n", need / 1e9, freeB / 1e9);
+    if (c->verbose) fprintf(stderr, "staramd: resident junction insertion needs up to %.1f GB, %.1f GB free\n", need / 1e9, freeB / 1e9);
     c->residentInsertKeepsKeys = (u64)freeB >= need;            // (free memory was asked for with the keys in place)
     return (u64)freeB >= need ? 1 : 0;
 }
@@ -614,8 +628,7 @@ extern "C" int staramd_set_novel_junctions(staramd_ctx *c, const uint64_t *start
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipDeviceSynchronize());
     DevIndex &X = c->X; int rc;
-    for (const u64 *old : {X.sjNovelStart, X.sjNovelEnd})
-        for (size_t i = 0; old && i < c->indexAllocs.size(); i++) if (c->indexAllocs[i] == (void *)old) { (void)hipFree(c->indexAllocs[i]); c->indexAllocs.erase(c->indexAllocs.begin() + i); break; }
+    devFree(c->indexAllocs, X.sjNovelStart); devFree(c->indexAllocs, X.sjNovelEnd);
     X.sjNovelStart = X.sjNovelEnd = nullptr; X.sjNovelN = 0;
     if ((rc = devUpload(c->indexAllocs, &X.sjNovelStart, (const u64 *)start, (u64)n, 1))) return rc;
     if ((rc = devUpload(c->indexAllocs, &X.sjNovelEnd, (const u64 *)end, (u64)n, 1))) return rc;
@@ -630,47 +643,17 @@ extern "C" void staramd_destroy(staramd_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    if (c->owner) { auto &v = c->owner->sharers; for (size_t i = 0; i < v.size(); i++) if (v[i] == c) { v.erase(v.begin() + i); break; } }
-    for (staramd_ctx *s : c->sharers) s->owner = nullptr;         // (their index is gone with this context: destroy the sharers first)
-    if (!c->owner) freeAll(c->indexAllocs);
-    freeAll(c->workAllocs);
-    for (int i = 0; i < 10; i++) (void)hipEventDestroy(c->ev[i]);
-    if (c->evWait) (void)hipEventDestroy(c->evWait);
-    if (c->evDownload) (void)hipEventDestroy(c->evDownload);
-    for (int k = 0; k < 2; k++) if (c->in[k].up) (void)hipEventDestroy(c->in[k].up);
-    if (c->copyStream) (void)hipStreamDestroy(c->copyStream);
-    if (c->hostScratch) (void)hipHostFree(c->hostScratch);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    teardown(c);
 }
 
-// grow a pool after an overflow of the bump allocator (the batch is then simply run again: inputs are resident)
 // grow a pool after an overflow of the bump allocator (the batch is then simply run again: inputs are resident).
 // The cursors keep counting past the capacity, so they tell the demand of the stage that overflowed.
 static int growPools(staramd_ctx *c, u32 flags, const u32 *cur) {
-    DevBatch &B = c->B; std::vector<void *> &R = c->workAllocs; int rc;
+    DevBatch &B = c->B; int rc;
     auto grow = [](u32 cap, u32 demand) { return (u32)std::min<u64>(std::max<u64>((u64)cap * 2, (u64)demand + demand / 4 + 1024), 0xFFFFFFF0ull); };
-    if (flags & OVF_SEEDPOOL) { B.seedCap = grow(B.seedCap, cur[CUR_SEED]); if ((rc = devRealloc(R, &B.seedPool, (u64)B.seedCap))) return rc; }
-    if (flags & OVF_WINPOOL) {
-        B.winCap = grow(B.winCap, std::max(cur[CUR_WIN], cur[CUR_ITEM])); B.waCap = grow(B.waCap, cur[CUR_WA]);
-        if ((rc = devRealloc(R, &B.winPool, (u64)B.winCap))) return rc;
-        if ((rc = devRealloc(R, &B.waPool, (u64)B.waCap))) return rc;
-        if ((rc = devRealloc(R, &B.wout, (u64)B.winCap))) return rc;
-        if ((rc = devRealloc(R, &B.items, (u64)B.winCap))) return rc;
-        if ((rc = devRealloc(R, &B.itemClass, (u64)B.winCap))) return rc;
-        if ((rc = devRealloc(R, &B.order, (u64)B.winCap + 64))) return rc;
-        if ((rc = devRealloc(R, &B.redoList, (u64)B.winCap))) return rc;
-        if ((rc = devRealloc(R, &B.replayList, (u64)B.winCap))) return rc;
-        if ((rc = devRealloc(R, &B.heavyList, (u64)B.winCap))) return rc;
-        if ((rc = devRealloc(R, &B.heavyList2, (u64)B.winCap))) return rc;
-    }
-    if (flags & OVF_TRPOOL) {
-        B.trCap = grow(B.trCap, cur[CUR_TR]); B.exCap = grow(B.exCap, cur[CUR_EX]);
-        if ((rc = devRealloc(R, &B.trPool, (u64)B.trCap))) return rc;
-        if ((rc = devRealloc(R, &B.exPool, (u64)B.exCap))) return rc;
-        if ((rc = devRealloc(R, &c->dOutTr, (u64)B.trCap))) return rc;
-        if ((rc = devRealloc(R, &c->dOutEx, (u64)B.exCap))) return rc;
-    }
+    if (flags & OVF_SEEDPOOL) { B.seedCap = grow(B.seedCap, cur[CUR_SEED]); if ((rc = devRealloc(c->workAllocs, &B.seedPool, (u64)B.seedCap))) return rc; }
+    if (flags & OVF_WINPOOL) { B.winCap = grow(B.winCap, std::max(cur[CUR_WIN], cur[CUR_ITEM])); B.waCap = grow(B.waCap, cur[CUR_WA]); if ((rc = allocWinPools(c))) return rc; }
+    if (flags & OVF_TRPOOL) { B.trCap = grow(B.trCap, cur[CUR_TR]); B.exCap = grow(B.exCap, cur[CUR_EX]); if ((rc = allocTrPools(c))) return rc; }
     return 0;
 }
 
@@ -680,6 +663,11 @@ static hipError_t waitStream(staramd_ctx *c) {
     return e != hipSuccess ? e : hipEventSynchronize(c->evWait);
 }
 
+// one launch of the cooperative stitcher over the batch in B: the shape's grid and LDS, the mode tells the kernel which work items are its own (k_stitch.hip)
+static void launchStitch(staramd_ctx *c, const StitchShape &sh, u32 ldsWords, u32 mode) {
+    hipLaunchKernelGGL(k_stitch_win, dim3(sh.blocks), dim3(256), stitchLds(c, sh, stitchReadBytes(ldsWords)), c->stream, c->dX, c->B, c->scrStitchBig, sh.depth, c->capRank, sh.arena, c->arenaBig,
+                       ldsWords, mode, c->prune);
+}
 // every kernel of a batch and the read-back of its totals, cursors and counters, enqueued; nothing is waited for
 static int enqueueAll(staramd_ctx *c) {
     c->nLaunches++;
@@ -688,99 +676,88 @@ static int enqueueAll(staramd_ctx *c) {
     HIPCHK(hipMemsetAsync(B.cursors, 0, CUR_N * sizeof(u32), s));
     HIPCHK(hipMemsetAsync(B.counters, 0, DC_N * sizeof(u64), s));
     HIPCHK(hipMemsetAsync(B.costHist, 0, 64 * sizeof(u32), s));
-    HIPCHK(hipMemsetAsync(B.candTops, 0, ((size_t)std::max(std::max(std::max(c->stBlocks, c->stBlocksMain), c->stBlocksLean), c->replayBlocks) * 4 + 64) * sizeof(u32), s));
+    HIPCHK(hipMemsetAsync(B.candTops, 0, ((size_t)c->maxStBlocks * 4 + 64) * sizeof(u32), s));
     dim3 block(256);
     u32 ldsWords = ((c->residentMaxLread + 7) / 8) | 1u;              // odd stride: conflict-free LDS staging
-    HIPCHK(hipEventRecord(c->ev[0], s));
+    HIPCHK(hipEventRecord(c->ev[EV_START], s));
     hipLaunchKernelGGL(k_seed_plan, dim3((n + 255) / 256), block, 0, s, c->dX, B, c->seedWork);
     hipLaunchKernelGGL(k_seed_units, dim3(c->seedUnitLanes / 256), block, 0, s, c->dX, B, c->seedWork);
     hipLaunchKernelGGL(k_seed_merge, dim3(std::min<u32>((n + 3) / 4, (u32)c->nCU * 8u)), block, 0, s, c->dX, B, c->seedWork);
     hipLaunchKernelGGL(k_seed_search, dim3(std::min<u32>(c->seedLanes / 256, (n + 255) / 256)), block, 0, s, c->dX, B, c->scrSeed, c->seedPerLane, (const u32 *)c->seedWork.handOn);      // what the units handed on (rarely anything)
-    HIPCHK(hipEventRecord(c->ev[1], s));
+    HIPCHK(hipEventRecord(c->ev[EV_SEED], s));
     {
         u32 blocks = std::max<u32>(1, std::min<u32>(c->winBlocks, (n + 3) / 4));
         const u32 useMid = (c->capWMid ? 1u : 0u) | (c->winOwnerMap ? 2u : 0u);
-        hipLaunchKernelGGL(k_windows, dim3(blocks), block, 4 * (c->capW * 8 + c->hashBits / 32) * sizeof(u32), s, c->dX, B, c->scrWin, c->capW, c->capBlocks, 0u, c->lightEst, useMid, c->hashBits);
-        HIPCHK(hipEventRecord(c->ev[7], s));
-        if (c->capWMid) hipLaunchKernelGGL(k_windows, dim3(c->winBlocksMid), dim3(64), (c->capWMid * 8 + c->hashBitsMid / 32) * sizeof(u32), s, c->dX, B, c->scrWinMid, c->capWMid, c->capBlocksMid, 2u, c->lightEst, useMid, c->hashBitsMid);
+        hipLaunchKernelGGL(k_windows, dim3(blocks), block, 4 * winLdsWords(c->capW, c->hashBits) * sizeof(u32), s, c->dX, B, c->scrWin, c->capW, c->capBlocks, 0u, c->lightEst, useMid, c->hashBits);
+        HIPCHK(hipEventRecord(c->ev[EV_WIN_FIRST], s));
+        if (c->capWMid) hipLaunchKernelGGL(k_windows, dim3(c->winBlocksMid), dim3(64), winLdsWords(c->capWMid, c->hashBitsMid) * sizeof(u32), s, c->dX, B, c->scrWinMid, c->capWMid, c->capBlocksMid, 2u, c->lightEst, useMid, c->hashBitsMid);
         hipLaunchKernelGGL(k_windows_big, dim3(c->winBlocksBig), block, 0, s, c->dX, B, c->scrWinBig, c->capWBig, c->capBlocksBig, c->lightEst, useMid);
-        HIPCHK(hipEventRecord(c->ev[5], s));
+        HIPCHK(hipEventRecord(c->ev[EV_WIN_TABLES], s));
         hipLaunchKernelGGL(k_order_hist, dim3(1024), block, 0, s, B);
         hipLaunchKernelGGL(k_order_offsets, dim3(1), dim3(1), 0, s, B);
         hipLaunchKernelGGL(k_order_scatter, dim3(1024), block, 0, s, B);
     }
-    HIPCHK(hipEventRecord(c->ev[2], s));
+    HIPCHK(hipEventRecord(c->ev[EV_WINDOWS], s));
     {
-        size_t readBytes = (ldsWords * 4u + 15u) & ~15u;
-        size_t ldsFast = 4 * (readBytes + stitchStateBytesH(c->capDepth, c->capRank, c->arenaFast));
-        const u32 prune = c->prune;
         // the lane kernel keeps the packed read of each of its 256 lanes in LDS: reads beyond ~512 bases (2x250 and longer) do not fit into what a block
         // may ask for, and the batch takes the cooperative launches alone (same results: the class cap only picks the kernel)
-        const bool laneFits = 256 * (size_t)ldsWords * 4 <= c->ldsLimit;
-        if (!(c->laneBlocks && laneFits)) HIPCHK(hipEventRecord(c->ev[8], s));
-        size_t ldsLean = c->leanDepth ? 4 * (readBytes + stitchStateBytesH(c->leanDepth, c->capRank, c->leanArena)) : 0;
-        for (u32 mode = 0; mode < 2; mode++) {
-            if (mode == 0 && c->laneBlocks && laneFits) {      // pass 0 in two launches: one LANE per read for the light reads of few seeds per window, the cooperative walk for the rest
-                // highest cost class the lane kernel takes (STARAMD_LANE_CLASS; 0 = by the kind of reads): 3 for paired-end reads, 5 for single-end ones, whose windows are cheap enough for a lane up
-                // to there (same box, ms of the stitch stage per 400 k: 2x101 at 3.1 Gb 14.5 / 15.7 / 16.5 / 18.2 at 3 / 4 / 5 / 6; 1x50 at 12 Mb 37.3 / 32.3 / 33.3 / 35.0 at 3 / 5 / 6 / 7: profiles/r06_ab_session7_*)
-                const u32 laneClass = c->laneClass ? c->laneClass : (c->X.P.readNmates == 2 ? 3u : 5u);
-                hipLaunchKernelGGL(k_stitch_lane, dim3(c->laneBlocks), block, 256 * (size_t)ldsWords * 4, s, c->dX, B, c->scrLane, c->laneArenaBytes, ldsWords, prune, laneClass);
-                HIPCHK(hipEventRecord(c->ev[8], s));
-                if (c->mainDepth) {     // the cooperative walk in two launches: windows of up to mainDepth - 1 seeds at four blocks per CU, the few that hold more at full depth
-                    const size_t ldsMain = 4 * (readBytes + stitchStateBytesH(c->mainDepth, c->capRank, c->arenaFast));
-                    hipLaunchKernelGGL(k_stitch_win, dim3(c->stBlocksMain), block, ldsMain, s, c->dX, B, c->scrStitchBig, c->mainDepth, c->capRank, c->arenaFast, c->arenaBig, ldsWords, 3u, prune);
-                    hipLaunchKernelGGL(k_stitch_win, dim3(c->stBlocks), block, ldsFast, s, c->dX, B, c->scrStitchBig, c->capDepth, c->capRank, c->arenaFast, c->arenaBig, ldsWords, 4u, prune);
-                } else
-                hipLaunchKernelGGL(k_stitch_win, dim3(c->stBlocks), block, ldsFast, s, c->dX, B, c->scrStitchBig, c->capDepth, c->capRank, c->arenaFast, c->arenaBig, ldsWords, 2u, prune);
-            } else
-            if (mode == 0 && c->leanDepth) {       // pass 0 in two launches: lean LDS slices for the windows of few seeds, full-size slices for the rest
-                hipLaunchKernelGGL(k_stitch_win, dim3(c->stBlocksLean), block, ldsLean, s, c->dX, B, c->scrStitchBig, c->leanDepth, c->capRank, c->leanArena, c->arenaBig, ldsWords, 0u, prune);
-                hipLaunchKernelGGL(k_stitch_win, dim3(c->stBlocks), block, ldsFast, s, c->dX, B, c->scrStitchBig, c->capDepth, c->capRank, c->arenaFast, c->arenaBig, ldsWords, 2u, prune);
-            } else
-            hipLaunchKernelGGL(k_stitch_win, dim3(c->stBlocks), block, ldsFast, s, c->dX, B, c->scrStitchBig, c->capDepth, c->capRank, c->arenaFast, c->arenaBig, ldsWords, mode, prune);
-            if (mode == 0) HIPCHK(hipEventRecord(c->ev[6], s));
-            if (mode == 0) {
-                hipLaunchKernelGGL(k_stitch_verify, dim3((n + 255) / 256), block, 0, s, c->dX, B);
-                hipLaunchKernelGGL(k_stitch_replay, dim3(c->replayBlocks), block, 4 * (size_t)stitchStateBytesH(0, c->capRank, c->arenaFast), s, c->dX, B, c->scrStitchBig, 0u, c->capRank, c->arenaFast, c->arenaBig, 0u);
-            }
+        const size_t ldsLane = 256 * (size_t)ldsWords * 4;
+        if (c->laneBlocks && ldsLane <= c->ldsLimit) {      // pass 0, the light reads of few seeds per window: one LANE per read; the cooperative walk for the rest
+            // highest cost class the lane kernel takes (STARAMD_LANE_CLASS; 0 = by the kind of reads): 3 for paired-end reads, 5 for single-end ones, whose windows are cheap enough for a lane up
+            // to there (same box, ms of the stitch stage per 400 k: 2x101 at 3.1 Gb 14.5 / 15.7 / 16.5 / 18.2 at 3 / 4 / 5 / 6; 1x50 at 12 Mb 37.3 / 32.3 / 33.3 / 35.0 at 3 / 5 / 6 / 7: profiles/r06_ab_session7_*)
+            const u32 laneClass = c->laneClass ? c->laneClass : (c->X.P.readNmates == 2 ? 3u : 5u);
+            hipLaunchKernelGGL(k_stitch_lane, dim3(c->laneBlocks), block, ldsLane, s, c->dX, B, c->scrLane, c->laneArenaBytes, ldsWords, c->prune, laneClass);
+            HIPCHK(hipEventRecord(c->ev[EV_LANE], s));
+            if (c->stMain.depth) {      // the cooperative walk in two launches: windows of up to depth - 1 seeds at four blocks per CU, the few that hold more at full depth
+                launchStitch(c, c->stMain, ldsWords, 3u);
+                launchStitch(c, c->stFull, ldsWords, 4u);
+            } else launchStitch(c, c->stFull, ldsWords, 2u);
+        } else {
+            HIPCHK(hipEventRecord(c->ev[EV_LANE], s));
+            if (c->stLean.depth) {      // pass 0 in two launches: lean LDS slices for the windows of few seeds, full-size slices for the rest
+                launchStitch(c, c->stLean, ldsWords, 0u);
+                launchStitch(c, c->stFull, ldsWords, 2u);
+            } else launchStitch(c, c->stFull, ldsWords, 0u);
         }
+        HIPCHK(hipEventRecord(c->ev[EV_PASS0], s));
+        hipLaunchKernelGGL(k_stitch_verify, dim3((n + 255) / 256), block, 0, s, c->dX, B);
+        hipLaunchKernelGGL(k_stitch_replay, dim3(c->stReplay.blocks), block, stitchLds(c, c->stReplay, 0), s, c->dX, B, c->scrStitchBig, 0u, c->capRank, c->stReplay.arena, c->arenaBig, 0u);
+        launchStitch(c, c->stFull, ldsWords, 1u);
         hipLaunchKernelGGL(k_stitch_finish, dim3((n + 255) / 256), block, 0, s, c->dX, B);
     }
-    HIPCHK(hipEventRecord(c->ev[3], s));
+    HIPCHK(hipEventRecord(c->ev[EV_STITCH], s));
     hipLaunchKernelGGL(k_scan_local, dim3((n + 255) / 256), block, 0, s, B, c->dTrBase, c->dExBase, c->dBlockTot);
     hipLaunchKernelGGL(k_scan_offsets, dim3(1), dim3(1024), 0, s, B, c->dBlockTot, (n + 255) / 256, c->dTotals);
     if (c->downloadPending) { HIPCHK(hipStreamWaitEvent(s, c->evDownload, 0)); c->downloadPending = false; }      // the results of the batch before may still be on their way out of dOut* (staramd_map_end)
     hipLaunchKernelGGL(k_gather, dim3((n + 255) / 256), block, 0, s, B, c->dTrBase, c->dExBase, c->dBlockTot, c->dOutReads, c->dOutTr, B.trCap, c->dOutEx, B.exCap);
-    HIPCHK(hipEventRecord(c->ev[4], s));
+    HIPCHK(hipEventRecord(c->ev[EV_END], s));
     HIPCHK(hipGetLastError());
     u32 *hs = c->hostScratch;
-    HIPCHK(hipMemcpyAsync(hs, c->dTotals, 2 * sizeof(u32), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hs + 8, B.cursors, CUR_N * sizeof(u32), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(hs + 8 + CUR_N, B.counters, DC_N * sizeof(u64), hipMemcpyDeviceToHost, s));      // pinned; collectAll copies them into c->counters: staramd_get_counters
+    HIPCHK(hipMemcpyAsync(hs + HS_TOTALS, c->dTotals, 2 * sizeof(u32), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hs + HS_CURSORS, B.cursors, CUR_N * sizeof(u32), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hs + HS_COUNTERS, B.counters, DC_N * sizeof(u64), hipMemcpyDeviceToHost, s));      // pinned; collectAll copies them into c->counters: staramd_get_counters
     return STARAMD_OK;                                                                                     // then always describes the last COLLECTED batch, whatever is in flight
 }
 // ... waited for: stage times, overflow flags
 static int collectAll(staramd_ctx *c, staramd_results *r, u32 *flagsOut) {
-    u32 *hs = c->hostScratch;
+    const u32 *cur = c->hostScratch + HS_CURSORS; hipEvent_t *ev = c->ev;
     HIPCHK(waitStream(c));
-    if (getenv("STARAMD_VERBOSE")) fprintf(stderr, "staramd: seed units %u in %u groups, reads handed on to k_seed_search %u; stitch work items %u, handed on by the lane kernel %u, by the main cooperative launch to the full-depth one %u\n", hs[8 + CUR_SEED_UNITS], hs[8 + CUR_SEED_GROUPS], hs[8 + CUR_OVF_SEED], hs[8 + CUR_ITEM], hs[8 + CUR_ST_HEAVY], hs[8 + CUR_ST_HEAVY2]);
-    HIPCHK(hipEventElapsedTime(&r->msSeed, c->ev[0], c->ev[1]));
-    HIPCHK(hipEventElapsedTime(&r->msWindows, c->ev[1], c->ev[2]));
-    HIPCHK(hipEventElapsedTime(&r->msStitch, c->ev[2], c->ev[3]));
-    HIPCHK(hipEventElapsedTime(&r->msTotalDevice, c->ev[0], c->ev[4]));
-    // [0] k_seed_search  [1] k_windows (both passes)  [2] k_order_*  [3] k_stitch_win pass 0  [4] verify + replay + re-walk + finish
-    // [5] scan + gather  [6] total
-    c->ms[0] = r->msSeed;
-    HIPCHK(hipEventElapsedTime(&c->ms[1], c->ev[1], c->ev[5]));
-    HIPCHK(hipEventElapsedTime(&c->ms[2], c->ev[5], c->ev[2]));
-    HIPCHK(hipEventElapsedTime(&c->ms[3], c->ev[2], c->ev[6]));
-    HIPCHK(hipEventElapsedTime(&c->ms[4], c->ev[6], c->ev[3]));
-    HIPCHK(hipEventElapsedTime(&c->ms[5], c->ev[3], c->ev[4]));
-    HIPCHK(hipEventElapsedTime(&c->ms[7], c->ev[7], c->ev[5]));        // [7] the middle + last k_windows launches alone (part of [1])
-    { float t6 = 0; HIPCHK(hipEventElapsedTime(&t6, c->ev[2], c->ev[8])); c->ms8 = t6; }      // [8] the k_stitch_lane launch alone (part of [3])
-    c->ms[6] = r->msTotalDevice;
-    *flagsOut = hs[8 + CUR_FLAGS];
-    memcpy(c->counters, hs + 8 + CUR_N, DC_N * sizeof(u64));
+    if (c->verbose) fprintf(stderr, "staramd: seed units %u in %u groups, reads handed on to k_seed_search %u; stitch work items %u, handed on by the lane kernel %u, by the main cooperative launch to the full-depth one %u\n", cur[CUR_SEED_UNITS], cur[CUR_SEED_GROUPS], cur[CUR_OVF_SEED], cur[CUR_ITEM], cur[CUR_ST_HEAVY], cur[CUR_ST_HEAVY2]);
+    HIPCHK(hipEventElapsedTime(&r->msSeed, ev[EV_START], ev[EV_SEED]));
+    HIPCHK(hipEventElapsedTime(&r->msWindows, ev[EV_SEED], ev[EV_WINDOWS]));
+    HIPCHK(hipEventElapsedTime(&r->msStitch, ev[EV_WINDOWS], ev[EV_STITCH]));
+    HIPCHK(hipEventElapsedTime(&r->msTotalDevice, ev[EV_START], ev[EV_END]));
+    c->ms[MS_SEED] = r->msSeed;                                                            // k_seed_*
+    HIPCHK(hipEventElapsedTime(&c->ms[MS_WIN_TABLES], ev[EV_SEED], ev[EV_WIN_TABLES]));    // k_windows (all launches)
+    HIPCHK(hipEventElapsedTime(&c->ms[MS_ORDER], ev[EV_WIN_TABLES], ev[EV_WINDOWS]));      // k_order_*
+    HIPCHK(hipEventElapsedTime(&c->ms[MS_PASS0], ev[EV_WINDOWS], ev[EV_PASS0]));           // k_stitch_lane + k_stitch_win pass 0
+    HIPCHK(hipEventElapsedTime(&c->ms[MS_REDECIDE], ev[EV_PASS0], ev[EV_STITCH]));         // verify + replay + re-walk + finish
+    HIPCHK(hipEventElapsedTime(&c->ms[MS_GATHER], ev[EV_STITCH], ev[EV_END]));             // scan + gather
+    c->ms[MS_TOTAL] = r->msTotalDevice;
+    HIPCHK(hipEventElapsedTime(&c->ms[MS_WIN_MID_BIG], ev[EV_WIN_FIRST], ev[EV_WIN_TABLES]));      // the middle + last k_windows launches alone (part of MS_WIN_TABLES)
+    HIPCHK(hipEventElapsedTime(&c->ms[MS_LANE], ev[EV_WINDOWS], ev[EV_LANE]));             // the k_stitch_lane launch alone (part of MS_PASS0)
+    *flagsOut = cur[CUR_FLAGS];
+    memcpy(c->counters, c->hostScratch + HS_COUNTERS, DC_N * sizeof(u64));
     return STARAMD_OK;
 }
 static int launchAll(staramd_ctx *c, staramd_results *r, u32 *flagsOut) {
@@ -789,36 +766,48 @@ static int launchAll(staramd_ctx *c, staramd_results *r, u32 *flagsOut) {
 }
 
 // the result arrays of the batch that was mapped last, into the caller's: totals first -- arrays that are too small are an error return, and the results stay where they are
-static int copyResults(staramd_ctx *c, staramd_results *r) {
-    DevBatch &B = c->B; hipStream_t s = c->stream; const u32 n = B.nReads;
-    const u32 *totals = c->hostScratch;
+static int resultsFit(staramd_ctx *c, staramd_results *r) {
+    const u32 *totals = c->hostScratch + HS_TOTALS;
     r->trCount = totals[0]; r->exCount = totals[1];
     if (totals[0] > r->trCapacity || totals[1] > r->exCapacity) { g_err = "result arrays too small: need " + std::to_string(totals[0]) + " transcripts, " + std::to_string(totals[1]) + " exons"; return STARAMD_ERR_RESULT_OVERFLOW; }
-    HIPCHK(hipMemcpyAsync(r->reads, c->dOutReads, (u64)n * sizeof(staramd_read_result), hipMemcpyDeviceToHost, s));
-    if (totals[0]) HIPCHK(hipMemcpyAsync(r->tr, c->dOutTr, (u64)totals[0] * sizeof(staramd_transcript), hipMemcpyDeviceToHost, s));
-    if (totals[1]) HIPCHK(hipMemcpyAsync(r->ex, c->dOutEx, (u64)totals[1] * sizeof(staramd_exon), hipMemcpyDeviceToHost, s));
+    return STARAMD_OK;
+}
+// ... then the three arrays, enqueued on stream s
+static int copyOut(staramd_ctx *c, staramd_results *r, hipStream_t s) {
+    HIPCHK(hipMemcpyAsync(r->reads, c->dOutReads, (u64)c->B.nReads * sizeof(staramd_read_result), hipMemcpyDeviceToHost, s));
+    if (r->trCount) HIPCHK(hipMemcpyAsync(r->tr, c->dOutTr, (u64)r->trCount * sizeof(staramd_transcript), hipMemcpyDeviceToHost, s));
+    if (r->exCount) HIPCHK(hipMemcpyAsync(r->ex, c->dOutEx, (u64)r->exCount * sizeof(staramd_exon), hipMemcpyDeviceToHost, s));
+    return STARAMD_OK;
+}
+static int copyResults(staramd_ctx *c, staramd_results *r) {
+    int rc = resultsFit(c, r);
+    if (!rc) rc = copyOut(c, r, c->stream);
+    if (rc) return rc;
     HIPCHK(waitStream(c));
     return STARAMD_OK;
 }
-static int runDevice(staramd_ctx *c, staramd_results *r) {
-    DevBatch &B = c->B; hipStream_t s = c->stream;
-    u32 n = B.nReads;
-    u32 flags = 0;
-    for (int attempt = 0;; attempt++) {
-        int rc = launchAll(c, r, &flags);
-        if (rc) return rc;
-        if (flags == 0) break;
-        const u32 *cur = c->hostScratch + 8;
+// a batch was collected with these overflow flags: while a pool has overflowed it is grown and the batch (its inputs are resident) run again
+static int rerunWhileOverflow(staramd_ctx *c, staramd_results *r, u32 flags) {
+    const DevBatch &B = c->B;
+    for (int attempt = 0; flags; attempt++) {
+        const u32 *cur = c->hostScratch + HS_CURSORS;
         if ((flags & OVF_HARD) || attempt >= 12) {
             char buf[320];
             snprintf(buf, sizeof(buf), "device work-space overflow (flags 0x%x): seeds %u/%u windows %u/%u WA %u/%u tr %u/%u ex %u/%u",
                      flags, cur[CUR_SEED], B.seedCap, cur[CUR_WIN], B.winCap, cur[CUR_WA], B.waCap, cur[CUR_TR], B.trCap, cur[CUR_EX], B.exCap);
             g_err = buf; return STARAMD_ERR_SCRATCH_OVERFLOW;
         }
-        rc = growPools(c, flags, cur);
+        int rc = growPools(c, flags, cur);
+        if (!rc) rc = launchAll(c, r, &flags);
         if (rc) return rc;
     }
-    return copyResults(c, r);
+    return STARAMD_OK;
+}
+static int runDevice(staramd_ctx *c, staramd_results *r) {
+    u32 flags = 0;
+    int rc = launchAll(c, r, &flags);
+    if (!rc) rc = rerunWhileOverflow(c, r, flags);
+    return rc ? rc : copyResults(c, r);
 }
 
 // an upload that was started for a batch which will not be mapped: waited for and forgotten (the sets are free again)
@@ -828,15 +817,15 @@ static void dropPrefetched(staramd_ctx *c) {
     c->in[0].pending = c->in[1].pending = false;
 }
 
-static int mapBatchImpl(staramd_ctx *c, const staramd_batch *b, staramd_results *r);
-static int runDevice(staramd_ctx *c, staramd_results *r);
-extern "C" int staramd_map_batch(staramd_ctx *c, const staramd_batch *b, staramd_results *r) {
-    if (!c || !b || !r || !r->reads) { g_err = "bad arguments"; return STARAMD_ERR_ARG; }
-    const int rc = mapBatchImpl(c, b, r);
-    if (rc != STARAMD_OK) dropPrefetched(c);        // after an error nothing uploaded ahead is trusted: the caller's next batch is uploaded by its own call
-    return rc;
+// the four arrays of a batch into an input set, enqueued on stream s: the bases from base0 on, the read offsets as they count from there
+static int uploadBatch(staramd_ctx::InSet &I, hipStream_t s, const staramd_batch *b, u64 base0, const u64 *offs) {
+    const u32 n = b->nReads;
+    HIPCHK(hipMemcpyAsync(I.bases, b->bases + base0, b->readOffset[n] - base0, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(I.readOffset, offs, (u64)(n + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(I.mate1, b->mate1Length, (u64)n * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(I.mm, b->mmMaxTotal, (u64)n * 2, hipMemcpyHostToDevice, s));
+    return STARAMD_OK;
 }
-
 // checks, upload (unless staramd_prefetch_batch has done it) and the packed copy of the reads: the batch is resident, nothing is waited for
 static int stageBatch(staramd_ctx *c, const staramd_batch *b) {
     // a batch may be a slice of a larger one (readOffset[0] > 0: the pieces of a WASP re-mapping batch): sized and uploaded from its own first base
@@ -862,16 +851,10 @@ static int stageBatch(staramd_ctx *c, const staramd_batch *b) {
             c->nPrefetchHits++;
         } else {                    // not prefetched: into the set that holds nothing pending (both pending: the older one is given up)
             use = !c->in[c->cur].pending ? c->cur : (!c->in[1 - c->cur].pending ? 1 - c->cur : c->cur);
-            staramd_ctx::InSet &I = c->in[use];
-            if (I.pending) HIPCHK(hipStreamSynchronize(c->copyStream));          // (an upload nobody asked for any more may still be writing into the set)
-            HIPCHK(hipMemcpyAsync(I.bases, b->bases + base0, nBases, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(I.readOffset, offs, (u64)(n + 1) * 8, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(I.mate1, b->mate1Length, (u64)n * 2, hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(I.mm, b->mmMaxTotal, (u64)n * 2, hipMemcpyHostToDevice, s));
+            if (c->in[use].pending) HIPCHK(hipStreamSynchronize(c->copyStream));          // (an upload nobody asked for any more may still be writing into the set)
+            const int rc = uploadBatch(c->in[use], s, b, base0, offs); if (rc) return rc;
         }
-        c->in[use].pending = false; c->cur = use;
-        c->dBases = c->in[use].bases; c->dReadOffset = c->in[use].readOffset; c->dMate1 = c->in[use].mate1; c->dMM = c->in[use].mm;
-        c->B.bases = c->dBases; c->B.readOffset = c->dReadOffset; c->B.mate1Length = c->dMate1; c->B.mmMaxTotal = c->dMM;
+        c->in[use].pending = false; useInSet(c, use);
     }
     c->B.nReads = n; c->residentReads = n; c->residentMaxLread = maxL;
     c->B.packed = c->dPacked; c->B.packWords = packWords;
@@ -929,6 +912,13 @@ static int mapBatchImpl(staramd_ctx *c, const staramd_batch *b, staramd_results 
     return rc;
 }
 
+extern "C" int staramd_map_batch(staramd_ctx *c, const staramd_batch *b, staramd_results *r) {
+    if (!c || !b || !r || !r->reads) { g_err = "bad arguments"; return STARAMD_ERR_ARG; }
+    const int rc = mapBatchImpl(c, b, r);
+    if (rc != STARAMD_OK) dropPrefetched(c);        // after an error nothing uploaded ahead is trusted: the caller's next batch is uploaded by its own call
+    return rc;
+}
+
 // ---- the two halves of staramd_map_batch (include/star_amd_async.h) ----
 extern "C" int staramd_map_begin(staramd_ctx *c, const staramd_batch *b) {
     if (!c || !b || b->nReads == 0) { g_err = "bad arguments"; return STARAMD_ERR_ARG; }
@@ -947,12 +937,7 @@ extern "C" int staramd_map_wait(staramd_ctx *c) {
     HIPCHK(hipSetDevice(c->device));
     u32 flags = 0;
     int rc = collectAll(c, &c->msRes, &flags);
-    for (int attempt = 0; !rc && flags; attempt++) {          // a pool overflowed: grown, and the batch (its inputs are resident) run again -- as staramd_map_batch does
-        const u32 *cur = c->hostScratch + 8;
-        if ((flags & OVF_HARD) || attempt >= 12) { g_err = "device work-space overflow (flags " + std::to_string(flags) + ")"; rc = STARAMD_ERR_SCRATCH_OVERFLOW; break; }
-        rc = growPools(c, flags, cur);
-        if (!rc) rc = launchAll(c, &c->msRes, &flags);
-    }
+    if (!rc) rc = rerunWhileOverflow(c, &c->msRes, flags);          // (as staramd_map_batch does)
     if (rc) { c->inFlight = false; dropPrefetched(c); return rc; }
     c->collected = true;
     return STARAMD_OK;
@@ -961,18 +946,12 @@ extern "C" int staramd_map_end(staramd_ctx *c, staramd_results *r, const staramd
     if (!c || !r || !r->reads) { g_err = "bad arguments"; return STARAMD_ERR_ARG; }
     if (!c->inFlight) { g_err = "no batch in flight: staramd_map_begin first"; return STARAMD_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    DevBatch &B = c->B; const u32 n = B.nReads;
     { const int rc = staramd_map_wait(c); if (rc) return rc; }
     r->msSeed = c->msRes.msSeed; r->msWindows = c->msRes.msWindows; r->msStitch = c->msRes.msStitch; r->msTotalDevice = c->msRes.msTotalDevice;
-    const u32 *totals = c->hostScratch;
-    r->trCount = totals[0]; r->exCount = totals[1];
-    if (totals[0] > r->trCapacity || totals[1] > r->exCapacity) { g_err = "result arrays too small: need " + std::to_string(totals[0]) + " transcripts, " + std::to_string(totals[1]) + " exons"; return STARAMD_ERR_RESULT_OVERFLOW; }   // (the batch stays in flight: call again with larger arrays)
+    { const int rc = resultsFit(c, r); if (rc) return rc; }        // (too small: the batch stays in flight, call again with larger arrays)
     // the results leave on the copy stream; the kernels of `next` start beside them (its k_gather, the only writer of dOut*, waits for the copy)
-    hipStream_t cs = c->copyStream;
-    HIPCHK(hipMemcpyAsync(r->reads, c->dOutReads, (u64)n * sizeof(staramd_read_result), hipMemcpyDeviceToHost, cs));
-    if (totals[0]) HIPCHK(hipMemcpyAsync(r->tr, c->dOutTr, (u64)totals[0] * sizeof(staramd_transcript), hipMemcpyDeviceToHost, cs));
-    if (totals[1]) HIPCHK(hipMemcpyAsync(r->ex, c->dOutEx, (u64)totals[1] * sizeof(staramd_exon), hipMemcpyDeviceToHost, cs));
-    HIPCHK(hipEventRecord(c->evDownload, cs));
+    { const int rc = copyOut(c, r, c->copyStream); if (rc) return rc; }
+    HIPCHK(hipEventRecord(c->evDownload, c->copyStream));
     c->downloadPending = true;
     c->inFlight = false; c->collected = false;
     int rcNext = STARAMD_OK;
@@ -995,13 +974,9 @@ extern "C" int staramd_prefetch_batch(staramd_ctx *c, const staramd_batch *b) {
     if (k < 0) return STARAMD_OK;                                                          // two batches waiting already, or the free set is being read by kernels
     HIPCHK(hipSetDevice(c->device));
     staramd_ctx::InSet &I = c->in[k];
-    const u32 n = b->nReads; hipStream_t cs = c->copyStream;
-    HIPCHK(hipMemcpyAsync(I.bases, b->bases, nBases, hipMemcpyHostToDevice, cs));
-    HIPCHK(hipMemcpyAsync(I.readOffset, b->readOffset, (u64)(n + 1) * 8, hipMemcpyHostToDevice, cs));
-    HIPCHK(hipMemcpyAsync(I.mate1, b->mate1Length, (u64)n * 2, hipMemcpyHostToDevice, cs));
-    HIPCHK(hipMemcpyAsync(I.mm, b->mmMaxTotal, (u64)n * 2, hipMemcpyHostToDevice, cs));
-    HIPCHK(hipEventRecord(I.up, cs));
-    I.hBases = b->bases; I.hReadOffset = b->readOffset; I.nReads = n; I.pending = true;
+    { const int rc = uploadBatch(I, c->copyStream, b, 0, b->readOffset); if (rc) return rc; }
+    HIPCHK(hipEventRecord(I.up, c->copyStream));
+    I.hBases = b->bases; I.hReadOffset = b->readOffset; I.nReads = b->nReads; I.pending = true;
     return STARAMD_OK;
 }
 
@@ -1026,8 +1001,8 @@ extern "C" int staramd_map_resident(staramd_ctx *c, staramd_results *r) {
 
 extern "C" int staramd_get_timings(staramd_ctx *c, float *out, int n) {
     if (!c || !out) return 0;
-    int k = n < 9 ? n : 9;
-    for (int i = 0; i < k; i++) out[i] = i < 8 ? c->ms[i] : c->ms8;
+    int k = n < (int)MS_N ? n : (int)MS_N;
+    for (int i = 0; i < k; i++) out[i] = c->ms[i];
     return k;
 }
 

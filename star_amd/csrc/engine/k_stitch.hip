@@ -788,15 +788,7 @@ __device__ static void finalizeTranscript(StitchCtx &c, u32 lane, Hdr h, const L
     { PROF_T0(); recordCandidate(P, lane, Score, gLength, rLength, ne, recSlot, x, ex, wr); PROF_ADD(c, 4); }
 }
 
-// per-window LDS work space, in bytes: undo stack, exon rows, leaf copy, rank list, seed list (+ arena in the fast path)
-#define REC_HDR_BYTES 96u
-// seed list rows (24 B) and compat masks (8 B): as many as the launch walks at most (capDepth - 1 seeds per window), never more than WA_MAX
-__host__ __device__ inline u32 waRows(u32 capDepth) { return capDepth == 0 ? (u32)WA_MAX : (capDepth - 1u < (u32)WA_MAX ? capDepth - 1u : (u32)WA_MAX); }
-__host__ __device__ inline u32 stitchStateBytes(u32 capDepth, u32 capRank, u32 arenaBytes) {
-    u32 b = capDepth * (u32)sizeof(SFrame) + 2u * STARAMD_MAX_N_EXONS * 32u + ((capRank * 2u + 31u) & ~31u) + waRows(capDepth) * 32u + REC_HDR_BYTES + arenaBytes;
-    return (b + 127u) & ~127u;
-}
-
+// per-window LDS work space (launch_geom.h: stitchStateBytes, waRows, REC_HDR_BYTES)
 struct LaneMem { LDS SFrame *stack; LDS staramd_exon *EX, *LEAF; LDS DWA *WA; LDS u64 *compat; LDS u64 *rec; LDS u16 *rank; LDS u8 *arena; };
 
 // next seed index > i whose bit is set in mask, nA if none
@@ -1007,7 +999,7 @@ extern "C" __global__ void __launch_bounds__(256, STITCH_WAVES) k_stitch_win(con
     const u32 lane = threadIdx.x & 63u;
     u32 waveInBlock = WAVE_INDEX(threadIdx.x >> 6), wavesPerBlock = blockDim.x >> 6;
     u32 stateBytes = stitchStateBytes(capDepth, capRank, arenaBytes);
-    u32 readBytes = (ldsWords * 4u + 15u) & ~15u;
+    u32 readBytes = stitchReadBytes(ldsWords);
     LaneMem m;
     StitchCtx c; c.X = &X; c.nGstitch = 0; c.nStitchCalls = c.nExtendCalls = c.nNodes = c.nLeaves = c.nLeavesBound = c.nLeavesEarly = 0;
 #ifdef STARAMD_SHADOW
@@ -1259,7 +1251,7 @@ extern "C" __global__ void __launch_bounds__(256) k_stitch_replay(const DevIndex
     const u32 lane = threadIdx.x & 63u;
     u32 waveInBlock = WAVE_INDEX(threadIdx.x >> 6), wavesPerBlock = blockDim.x >> 6;
     u32 stateBytes = stitchStateBytes(capDepth, capRank, arenaBytes);
-    u32 readBytes = (ldsWords * 4u + 15u) & ~15u;
+    u32 readBytes = stitchReadBytes(ldsWords);
     LaneMem m;
     laneSetup((LDS u8 *)ldsReads + waveInBlock * (readBytes + stateBytes) + readBytes, capDepth, capRank, m);
     WinRec wr; wr.rank = m.rank; wr.arenaL = m.arena; wr.arenaBytesL = arenaBytes; wr.arenaG = bigArena + (u64)(blockIdx.x * wavesPerBlock + waveInBlock) * bigArenaBytes; wr.arenaBytesG = bigArenaBytes;

@@ -24,7 +24,7 @@
 //     new bin is a wave-wide max/min reduction over the table rows.
 // Reads that need more windows / seed-list blocks than the compact per-wave work space are deferred to a second
 // launch of the same kernel (big = 1) whose table lives in global memory with the reference's own limits.
-#include "dev.h"
+#include "launch_geom.h"              // WBITS, winLdsWords, winWaveBytes
 
 #define NOWIN 0xFFFFFFFFu
 static_assert(sizeof(DWin) == 16, "a window record is two 8-byte words (emission stores it as such)");
@@ -47,7 +47,6 @@ template <bool BIG> struct WTab {   // per-wave window table
     typename WPtr<BIG>::P coreS, coreE, extS, extE, meta, blk, lrec, nwa;
 };
 // meta = chr << 2 | str << 1 | alive
-#define WBITS 4096u                 // per-read hash bitmap of the bins covered by windows (quick reject of loci outside every window): bits in the first and last launch
 template <bool BIG> struct WS {
     WTab<BIG> t; DWA *arena; typename WPtr<BIG>::P bitmap;
     u32 nW, capW, nBlocks, capBlocks, Lread;
@@ -263,16 +262,7 @@ template <bool BIG> __device__ static u32 ownerWave(const WS<BIG> &s, u32 str, u
     return flank != NOWIN ? flank : core;
 }
 
-// per-wave work space in global memory: [table rows + bitmap (big pass only)] [seed-list blocks]
-__host__ __device__ inline u64 winWaveBytes(u32 capW, u32 capBlocks, u32 big) {
-    u64 b = (u64)capBlocks * WA_MAX * sizeof(DWA);
-    if (big) b += (u64)capW * 8 * sizeof(u32) + WBITS / 8;
-    return (b + 255) & ~255ull;
-}
-
-
-
-extern __shared__ u32 ldsTab[];     // LDS launches: wavesPerBlock * (capW * 8 + hashBits / 32) words
+extern __shared__ u32 ldsTab[];     // LDS launches: wavesPerBlock * winLdsWords(capW, hashBits) words; work space in global memory: winWaveBytes (launch_geom.h)
 
 // mode 0: every read, table in LDS (capW rows); reads that outgrow it go to list ovfWin
 // mode 2: the reads of ovfWin, table still in LDS but with more rows (blocks of one wavefront); reads that outgrow that go to list ovfWin2
@@ -289,7 +279,7 @@ template <bool BIG> __device__ __forceinline__ void windowsBody(const DevIndex *
     u8 *mine = scratch + (u64)wave * winWaveBytes(capW, capBlocks, big);
     typename WPtr<BIG>::P tab;
     if constexpr (BIG) tab = (u32 *)(mine + (u64)capBlocks * WA_MAX * sizeof(DWA));
-    else tab = (typename WPtr<false>::P)ldsTab + waveInBlock * (capW * 8 + hashBits / 32);
+    else tab = (typename WPtr<false>::P)ldsTab + waveInBlock * winLdsWords(capW, hashBits);
     s.hashMask = hashBits - 1u;
     s.bitmap = tab + capW * 8;
     s.t.coreS = tab; s.t.coreE = tab + capW; s.t.extS = tab + 2 * capW; s.t.extE = tab + 3 * capW;

@@ -1,16 +1,9 @@
 // stitch_common.h -- state and accessors shared by the cooperative stitcher (k_stitch.hip) and the scalar
 // restatement kept for the shadow-validation build (stitch_scalar.h).
 #pragma once
-#include "dev.h"
+#include "launch_geom.h"                   // Hdr, SFrame
 
 extern __shared__ u32 ldsReads[];          // blockDim.x * ldsWords 32-bit words: 4-bit packed read of every lane
-
-struct Hdr {                               // transcript header + walk position, kept in registers
-    u64 gStart, tG2;
-    u32 nExons; i32 Score;
-    u32 nMatch, nMM, nGap, lGap, nDel, lDel, nIns, lIns, nUnique, nAnchor, rStart, tR2;
-};
-struct SFrame { Hdr h; u32 iA; u32 pad; staramd_exon eA; };      // 112 bytes
 
 // nodes / leaves / stitch / extend call counters are diagnostics: they cost registers in a kernel that is 37 VGPRs over its budget,
 // so only the profile and shadow builds keep them (bench.py --profile-sections reports them); the genome-bytes counter stays
