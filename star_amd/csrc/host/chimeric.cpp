@@ -321,7 +321,7 @@ bool chimericDetectionOld(const RunParams &P, const GenomeIndex &gi, const ReadB
         out.push_back('\t'); appendU(out, chimRepeat0); out.push_back('\t'); appendU(out, chimRepeat1); out.push_back('\t'); out += b.name(ir);
         out.push_back('\t'); appendU(out, trChim[0].ex[0].G - c0 + 1); out.push_back('\t'); out += cigarP(trChim[0], readLengthOriginal, readLengthPair, nMates);
         out.push_back('\t'); appendU(out, trChim[1].ex[0].G - c1 + 1); out.push_back('\t'); out += cigarP(trChim[1], readLengthOriginal, readLengthPair, nMates);
-        if (std::find(P.outSAMattrOrder.begin(), P.outSAMattrOrder.end(), "RG") != P.outSAMattrOrder.end()) { out.push_back('\t'); out += P.outSAMattrRG.at(b.fileOf(ir)); }   // outSAMattrPresent.RG (:68)
+        if (P.attrHasRG) { out.push_back('\t'); out += P.outSAMattrRG.at(b.fileOf(ir)); }   // outSAMattrPresent.RG (:68)
         out.push_back('\n');
         return true;
     }
@@ -438,7 +438,6 @@ bool chimericDetectionMult(const RunParams &P, const GenomeIndex &gi, const Read
     if (chimN > C.multimapNmax) return false;
     const uint64_t readLengthOriginal[2] = {merged ? Lread : (uint64_t)b.seqSpan[0][ir].len, nMates == 2 ? (uint64_t)b.seqSpan[1][ir].len : 0};
     const uint64_t readLengthPair = nMates == 2 ? readLengthOriginal[0] + readLengthOriginal[1] + 1 : readLengthOriginal[0];
-    const bool rgColumn = std::find(P.outSAMattrOrder.begin(), P.outSAMattrOrder.end(), "RG") != P.outSAMattrOrder.end();
     auto appendI = [&](int v) { if (v < 0) { out.push_back('-'); appendU(out, (uint64_t)(-(int64_t)v)); } else appendU(out, (uint64_t)v); };
     for (size_t i = 0; i < chimAligns.size(); i++) {
         const ChimAlign &ca = chimAligns[i];
@@ -458,7 +457,7 @@ bool chimericDetectionMult(const RunParams &P, const GenomeIndex &gi, const Read
         out.push_back('\t'); appendU(out, ca.a2.ex[0].G - c2 + 1); out.push_back('\t'); out += cigarP(ca.a2, readLengthOriginal, readLengthPair, nMates);
         out.push_back('\t'); appendU(out, chimN); out.push_back('\t'); appendI(maxPossibleAlignScore); out.push_back('\t'); appendI(maxNonChimAlignScore);
         out.push_back('\t'); appendI(ca.chimScore); out.push_back('\t'); appendI(chimScoreBest); out += merged ? "\t1" : "\t0";       // PEmerged_bool
-        if (rgColumn) { out.push_back('\t'); out += P.outSAMattrRG.at(nb.fileOf(nir)); }
+        if (P.attrHasRG) { out.push_back('\t'); out += P.outSAMattrRG.at(nb.fileOf(nir)); }
         out.push_back('\n');
     }
     return chimN > 0;

@@ -14,6 +14,8 @@
 #include <cstdio>
 #include <istream>
 #include <string_view>
+#include <algorithm>
+#include <cassert>
 #include "../../../include/star_amd.h"
 #include "../../../include/star_amd_index.h"
 
@@ -63,6 +65,20 @@ struct WigParams {                     // --outWigType / --outWigStrand / --outW
     bool yes = false; int format = 0, type = 0, norm = 1; bool strand = true; std::string referencesPrefix;
 };
 
+// --outSAMattributes: the 17 accepted tags as codes.  --outSAMattributes takes at most SAM_ATTR_LISTED_MAX of them, parse() appends at most RG, XS, vW and NM
+enum class SamAttr : uint8_t { NH, HI, AS, nM, jM, jI, XS, NM, MD, MC, RG, ch, vA, vG, vW, rB, cN, OTHER };
+inline constexpr const char *SAM_ATTR_NAME[(int)SamAttr::OTHER] = {"NH", "HI", "AS", "nM", "jM", "jI", "XS", "NM", "MD", "MC", "RG", "ch", "vA", "vG", "vW", "rB", "cN"};
+inline SamAttr samAttrCode(const std::string &a) { for (int k = 0; k < (int)SamAttr::OTHER; k++) if (a == SAM_ATTR_NAME[k]) return (SamAttr)k; return SamAttr::OTHER; }
+constexpr uint32_t SAM_ATTR_LISTED_MAX = 26, SAM_ATTR_SLOTS = 32;
+static_assert(SAM_ATTR_LISTED_MAX + 4 <= SAM_ATTR_SLOTS, "the listed attributes and the four that parse() may add must fit the code list");
+struct SamAttrList {
+    SamAttr code[SAM_ATTR_SLOTS]; uint32_t n = 0;
+    void add(SamAttr a) { assert(n < SAM_ATTR_SLOTS); code[n++] = a; }
+    const SamAttr *begin() const { return code; }
+    const SamAttr *end() const { return code + n; }
+    bool has(SamAttr a) const { return std::find(begin(), end(), a) != end(); }
+};
+
 struct RunParams {
     staramd_params dev;                 // what reaches the device hot path
     // run
@@ -94,9 +110,10 @@ struct RunParams {
     bool outSAMmodeNoQS = false;
     bool outBAMunsorted = false, outBAMcoord = false; bool outSAMnone = false; int outBAMcompression = 1;   // --outSAMtype BAM Unsorted | None, --outBAMcompression
     bool gpuBAMdevice = false;           // --gpuBAMcompression Device: BAM records deflated on the MI355X through the hook of setBgzfDeviceFn
-    std::vector<std::string> outSAMattrOrder = {"NH", "HI", "AS", "nM"};   // Standard
-    bool attrNMorMD = false, attrHasCh = false;
-    std::vector<std::string> outSAMattrOrderQuant;   // attributes of Aligned.toTranscriptome.out.bam: NH HI, then RG / MC if requested (Parameters_samAttributes.cpp:43-47,96-111)
+    std::vector<std::string> outSAMattrOrder = {"NH", "HI", "AS", "nM"};   // Standard; the parsed list, read by the checks of parse()
+    // the list as codes, the list of Aligned.toTranscriptome.out.bam, and what the record writers ask of the list: decoded once, at the end of parse()
+    SamAttrList outSAMattrCodes, outSAMattrCodesQuant;
+    bool attrNMorMD = false, attrHasCh = false, attrWantJ = false, attrHasCN = false, attrHasRG = false;
     std::string readNameSeparator = "/";
     uint64_t gpuBatchReads = 65536;      // reads per device batch (ours; --gpuBatchReads)
     int gpuDevice = 0;

@@ -205,8 +205,8 @@ std::string RunParams::parse(int argc, char **argv) {
             if (v.size() == 1 && v[0] == "Standard") outSAMattrOrder = {"NH", "HI", "AS", "nM"};
             else if (v.size() == 1 && v[0] == "None") outSAMattrOrder.clear();
             else if (v.size() >= 1 && v[0] == "All") { outSAMattrOrder = {"NH", "HI", "AS", "nM", "NM", "MD", "jM", "jI", "MC", "ch"}; }   // + ch (Parameters_samAttributes.cpp:51-52)
-            else { outSAMattrOrder.clear(); for (auto &t : v) { if (t == "NH" || t == "HI" || t == "AS" || t == "nM" || t == "jM" || t == "jI" || t == "XS" || t == "NM" || t == "MD" || t == "MC" || t == "RG" || t == "ch" || t == "vA" || t == "vG" || t == "vW" || t == "rB" || t == "cN") outSAMattrOrder.push_back(t); else err = "EXITING: unsupported SAM attribute " + t; } }
-            if (outSAMattrOrder.size() > 26) err = "EXITING because of fatal PARAMETERS error: --outSAMattributes lists more than 26 attributes";      // (+ up to 4 added below; the formatter holds 32)
+            else { outSAMattrOrder.clear(); for (auto &t : v) { if (samAttrCode(t) != SamAttr::OTHER) outSAMattrOrder.push_back(t); else err = "EXITING: unsupported SAM attribute " + t; } }
+            if (outSAMattrOrder.size() > SAM_ATTR_LISTED_MAX) err = "EXITING because of fatal PARAMETERS error: --outSAMattributes lists more than " + std::to_string(SAM_ATTR_LISTED_MAX) + " attributes";      // (RG, XS, vW and NM may be added below: SAM_ATTR_SLOTS, host.h)
         }
         else if (k == "outSAMstrandField") { const std::string &s = one(k, v); if (s == "intronMotif") { dev.outSAMstrandFieldIntronMotif = 1; } else if (s != "None") err = "EXITING: unsupported --outSAMstrandField " + s; }
         else if (k == "outSAMprimaryFlag") { const std::string &s = one(k, v); if (s == "AllBestScore") outSAMprimaryAllBest = true; else if (s != "OneBestScore") err = "EXITING: unsupported --outSAMprimaryFlag " + s; }
@@ -444,9 +444,17 @@ std::string RunParams::parse(int argc, char **argv) {
         if (chim.multimapNmax == 0 && (chim.outJunctions || chim.outSamOld)) return "EXITING because of fatal PARAMETERS error: --chimMultimapNmax 0 (default old chimeric detection) and --peOverlapNbasesMin > 0 (merging ovelrapping mates) presently only works with --chimOutType WithinBAM\nSOLUTION: re-run with --chimOutType WithinBAM\n";
     }
     if (attrHasCh && !outBAMunsorted && !outBAMcoord) return "EXITING because of fatal PARAMETER error: --outSAMattributes contains ch tag, which requires BAM output.\nSOLUTION: re-run STAR with --outSAMtype BAM Unsorted (and/or) SortedByCoordinate option, or without ch tag in --outSAMattributes\n";
-    outSAMattrOrderQuant = {"NH", "HI"};
-    for (const std::string &a : outSAMattrOrder) if (a == "RG" || a == "MC" || a == "rB" || a == "cN" || (a == "vW" && vWquant)) outSAMattrOrderQuant.push_back(a);
-    attrNMorMD = std::find(outSAMattrOrder.begin(), outSAMattrOrder.end(), "NM") != outSAMattrOrder.end() || std::find(outSAMattrOrder.begin(), outSAMattrOrder.end(), "MD") != outSAMattrOrder.end();
+    // the list is final here: as codes for the record writers (postmap.cpp, chimeric.cpp), with what they ask of it, and the list of Aligned.toTranscriptome.out.bam:
+    // NH HI, then what was asked for of RG MC rB cN, and a vW that --waspOutputMode added (Parameters_samAttributes.cpp:43-47,96-111)
+    outSAMattrCodes = SamAttrList(); outSAMattrCodesQuant = SamAttrList();
+    outSAMattrCodesQuant.add(SamAttr::NH); outSAMattrCodesQuant.add(SamAttr::HI);
+    for (const std::string &a : outSAMattrOrder) {
+        const SamAttr c = samAttrCode(a);
+        outSAMattrCodes.add(c);
+        if (c == SamAttr::RG || c == SamAttr::MC || c == SamAttr::rB || c == SamAttr::cN || (c == SamAttr::vW && vWquant)) outSAMattrCodesQuant.add(c);
+    }
+    attrNMorMD = outSAMattrCodes.has(SamAttr::NM) || outSAMattrCodes.has(SamAttr::MD);
+    attrWantJ = outSAMattrCodes.has(SamAttr::jM) || outSAMattrCodes.has(SamAttr::jI); attrHasCN = outSAMattrCodes.has(SamAttr::cN); attrHasRG = outSAMattrCodes.has(SamAttr::RG);
     if (genomeDir.empty()) return "EXITING: --genomeDir is required";
     dev.readNmates = (uint32_t)readFilesIn.size();
     if (readFilesSAMmates > 0) {

@@ -3,9 +3,12 @@
 //   mappedFilter           source/ReadAlign_mappedFilter.cpp:3-21
 //   outputAlignments       source/ReadAlign_outputAlignments.cpp:5-72  (recordSJ :76-87, writeSAM :132-256)
 //   outputTranscriptSAM    source/ReadAlign_outputTranscriptSAM.cpp:5-359
+//   alignBAM               source/ReadAlign_alignBAM.cpp:9-614
 //   outputTranscriptSJ     source/ReadAlign_outputTranscriptSJ.cpp:4-56
 //   Stats::transcriptStats source/Stats.cpp:35-56
-// Host-side integer code; defines the parity surface (Aligned.out.sam, SJ.out.tab, Log.final.out).
+// Host-side integer code; defines the parity surface (Aligned.out.sam, the BAM outputs, SJ.out.tab, Log.final.out).
+// The SAM and the BAM record come from one derivation ("what the SAM and the BAM record of an alignment share", below): mateSpans (mates, clips, MAPQ, common flag
+// bits, PNEXT, TLEN), walkMate (CIGAR and jM / jI, into SamTextSink / BamSink), tagsNMandMD, unmappedMate; the attribute lists arrive as codes (RunParams, params.cpp).
 #include "host.h"
 #include <fstream>
 #include <cstring>
@@ -15,13 +18,19 @@
 namespace staramd {
 
 namespace {
-inline void appendUint(std::string &s, uint64_t v) {
-    char buf[24]; int n = 0;
-    do { buf[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-    while (n) s.push_back(buf[--n]);
+// numbers two digits at a time
+struct Digits2 { char d[200]; Digits2() { for (int i = 0; i < 100; i++) { d[2 * i] = (char)('0' + i / 10); d[2 * i + 1] = (char)('0' + i % 10); } } };
+const Digits2 DIG2;
+inline char *putUint(char *p, uint64_t v) {
+    char buf[24]; int n = 24;
+    while (v >= 100) { const uint64_t q = v / 100; const unsigned r = (unsigned)(v - q * 100); v = q; n -= 2; buf[n] = DIG2.d[2 * r]; buf[n + 1] = DIG2.d[2 * r + 1]; }
+    if (v >= 10) { n -= 2; buf[n] = DIG2.d[2 * v]; buf[n + 1] = DIG2.d[2 * v + 1]; } else buf[--n] = (char)('0' + v);
+    memcpy(p, buf + n, (size_t)(24 - n));
+    return p + (24 - n);
 }
-inline void appendInt(std::string &s, int64_t v) { if (v < 0) { s.push_back('-'); appendUint(s, (uint64_t)(-v)); } else appendUint(s, (uint64_t)v); }
-
+inline char *putInt(char *p, int64_t v) { if (v < 0) { *p++ = '-'; return putUint(p, (uint64_t)(-v)); } return putUint(p, (uint64_t)v); }
+inline void appendUint(std::string &s, uint64_t v) { char buf[24]; s.append(buf, (size_t)(putUint(buf, v) - buf)); }
+inline void appendInt(std::string &s, int64_t v) { char buf[24]; s.append(buf, (size_t)(putInt(buf, v) - buf)); }
 
 struct TrView {                 // one candidate alignment = header + exon slice of the result arrays
     const staramd_transcript *t; const staramd_exon *ex;
@@ -66,18 +75,8 @@ std::string PostMap::samHeader() const {                 // samHeaders.cpp:27-98
 // lines), numbers two digits at a time, the reverse complement through a byte table: with std::string appends character by character this function
 // was 97 % of the post-map stage (1.9 us per pair and thread; tools/host_bench.py).
 namespace {
-struct Digits2 { char d[200]; Digits2() { for (int i = 0; i < 100; i++) { d[2 * i] = (char)('0' + i / 10); d[2 * i + 1] = (char)('0' + i % 10); } } };
-const Digits2 DIG2;
 struct RcTable { char t[256]; RcTable() { for (int c = 0; c < 256; c++) t[c] = rcNt((char)c); } };
 const RcTable RCT;
-inline char *putUint(char *p, uint64_t v) {
-    char buf[24]; int n = 24;
-    while (v >= 100) { const uint64_t q = v / 100; const unsigned r = (unsigned)(v - q * 100); v = q; n -= 2; buf[n] = DIG2.d[2 * r]; buf[n + 1] = DIG2.d[2 * r + 1]; }
-    if (v >= 10) { n -= 2; buf[n] = DIG2.d[2 * v]; buf[n + 1] = DIG2.d[2 * v + 1]; } else buf[--n] = (char)('0' + v);
-    memcpy(p, buf + n, (size_t)(24 - n));
-    return p + (24 - n);
-}
-inline char *putInt(char *p, int64_t v) { if (v < 0) { *p++ = '-'; return putUint(p, (uint64_t)(-v)); } return putUint(p, (uint64_t)v); }
 inline char *putStr(char *p, const char *s, size_t n) { memcpy(p, s, n); return p + n; }
 inline char *putSv(char *p, std::string_view s) { memcpy(p, s.data(), s.size()); return p + s.size(); }
 template <size_t N> inline char *putLit(char *p, const char (&s)[N]) { memcpy(p, s, N - 1); return p + (N - 1); }
@@ -110,127 +109,181 @@ __attribute__((target("avx2"))) static void revCompCopyAvx2(char *dst, const cha
 static const bool HAVE_AVX2 = __builtin_cpu_supports("avx2") && !getenv("STARAMD_NO_AVX2");
 inline void revCopy(char *dst, const char *src, size_t n) { if (HAVE_AVX2) revCopyAvx2(dst, src, n); else for (size_t k = 0; k < n; k++) dst[k] = src[n - 1 - k]; }
 inline void revCompCopy(char *dst, const char *src, size_t n) { if (HAVE_AVX2) revCompCopyAvx2(dst, src, n); else for (size_t k = 0; k < n; k++) dst[k] = RCT.t[(uint8_t)src[n - 1 - k]]; }
-enum SamAttr : uint8_t { A_NH, A_HI, A_AS, A_nM, A_jM, A_jI, A_XS, A_NM, A_MD, A_MC, A_RG, A_OTHER };
-inline SamAttr samAttrCode(const std::string &a) {
-    static const char *names[] = {"NH", "HI", "AS", "nM", "jM", "jI", "XS", "NM", "MD", "MC", "RG"};
-    for (int k = 0; k < 11; k++) if (a == names[k]) return (SamAttr)k;
-    return A_OTHER;
+} // namespace
+
+// ================= what the SAM and the BAM record of an alignment share =================
+// The reference formats an alignment twice (ReadAlign_outputTranscriptSAM.cpp, ReadAlign_alignBAM.cpp) and its two writers do not agree everywhere: what they derive
+// alike is derived here, once; each difference is a switch that is named where it is used, with the reference's lines.
+namespace {
+// The mates of an alignment: the exons of each, its soft clips (ReadAlign_calcCIGAR.cpp:14-23,52-56), MAPQ and the flag bits that both writers set alike
+// (outputTranscriptSAM.cpp:62-135, alignBAM.cpp:187-283; not among them: 0x2 and 0x800, see samMapped / bamMapped), PNEXT and TLEN of a two-mate alignment
+struct MateSpans {
+    bool flagPaired; uint32_t nMates, iExMate, leftMate; int MAPQ;
+    uint64_t tlen;                                                                      // --outSAMtlen 1: + for the first mate in the alignment, - for the second
+    struct Span { uint32_t iEx1, iEx2, Mate, flag; uint64_t trimL1, trimR1, pnextG; } m[2] = {};     // m[1] of a one-mate alignment stays zero
+};
+inline MateSpans mateSpans(const RunParams &P, const GenomeIndex &gi, const ReadCtx &rc, const TrView &tv, uint64_t nTrOut, const ChimBam *chim) {
+    const staramd_transcript &t = *tv.t; const staramd_exon *ex = tv.ex;
+    const uint32_t nEx = t.nExons, Str = t.Str;
+    MateSpans s;
+    s.flagPaired = rc.nMates == 2; s.nMates = 1;
+    for (s.iExMate = 0; s.iExMate + 1 < nEx; s.iExMate++) if (ex[s.iExMate].canonSJ == -3) { s.nMates = 2; break; }
+    s.leftMate = s.flagPaired ? Str : 0;
+    s.MAPQ = P.outSAMmapqUnique;
+    if (nTrOut >= 5) s.MAPQ = 0; else if (nTrOut >= 3) s.MAPQ = 1; else if (nTrOut == 2) s.MAPQ = 3;
+    s.tlen = ex[nEx - 1].G + ex[nEx - 1].L - ex[0].G;
+    uint32_t common = 0;
+    if (s.flagPaired) { common = 0x0001; if (s.nMates == 1 && (!chim || chim->mateChr > gi.view.nChrReal)) common |= 0x0008; }      // no mate given: (uint)-1 > nChrReal (:75)
+    if (rc.b->filter[rc.i] == 'Y') common |= 0x200;
+    if (!tv.primary) common |= 0x100;
+    for (uint32_t imate = 0; imate < s.nMates; imate++) {
+        MateSpans::Span &m = s.m[imate];
+        m.iEx1 = imate == 0 ? 0 : s.iExMate + 1; m.iEx2 = imate == 0 ? s.iExMate : nEx - 1;
+        m.Mate = ex[m.iEx1].iFrag; m.pnextG = s.nMates == 2 ? ex[imate == 0 ? s.iExMate + 1 : 0].G : 0;
+        m.flag = common;
+        if (m.Mate == 0) { m.flag |= Str * 0x10; if (s.nMates == 2) m.flag |= (1 - Str) * 0x20; }
+        else { m.flag |= (1 - Str) * 0x10; if (s.nMates == 2) m.flag |= Str * 0x20; }
+        if (s.flagPaired) { m.flag |= (m.Mate == 0 ? 0x0040 : 0x0080); if (s.nMates == 1 && chim && chim->mateStrand == 1) m.flag |= 0x20; }     // :120-123
+        const uint64_t trimL = rc.trimL(Str, m.Mate);
+        m.trimL1 = trimL + ex[m.iEx1].R - (ex[m.iEx1].R < rc.readLength[s.leftMate] ? 0 : rc.readLength[s.leftMate] + 1);
+        m.trimR1 = (ex[m.iEx1].R < rc.readLength[s.leftMate] ? rc.readLengthOriginal[s.leftMate] : rc.readLength[s.leftMate] + 1 + rc.readLengthOriginal[m.Mate])
+                   - ex[m.iEx2].R - ex[m.iEx2].L - trimL;
+    }
+    return s;
+}
+
+// One walk over the exons of a mate (ReadAlign_calcCIGAR.cpp:3-58 = outputTranscriptSAM.cpp:137-176 = alignBAM.cpp:233-274): the gap rules are here and nowhere else.
+// The sink, a plain struct the compiler sees through, gets clip(length, side: 0 left, 1 right), op(length, CIG_*) -- the M of a zero-length block too --,
+// junction(motif, first, last base of the intron counted from chrS + 1), motif + 20: annotated (SJ_SAM_AnnotatedMotifShift), or noJunction() for a mate without any
+enum : uint32_t { CIG_M = 0, CIG_I = 1, CIG_D = 2, CIG_N = 3, CIG_S = 4, CIG_H = 5 };     // BAM operation codes = position of the letter
+const char CIG_LETTER[] = "MIDNSH";
+template <class Sink> inline void walkMate(const staramd_exon *ex, const MateSpans::Span &m, uint64_t chrS, Sink &sink) {
+    bool junctions = false;
+    if (m.trimL1 > 0) sink.clip(m.trimL1, 0);
+    for (uint32_t ii = m.iEx1; ii <= m.iEx2; ii++) {
+        if (ii > m.iEx1) {
+            const staramd_exon &a = ex[ii - 1];
+            const uint64_t gapG = ex[ii].G - (a.G + a.L);
+            const uint64_t gapR = (uint64_t)ex[ii].R - a.R - a.L;
+            if (gapR > 0) sink.op(gapR, CIG_I);                                  // an I and a D or N at the same gap are possible
+            if (a.canonSJ >= 0 || a.sjAnnot == 1) {
+                sink.op(gapG, CIG_N);
+                sink.junction(a.canonSJ + (a.sjAnnot == 0 ? 0 : 20), a.G + a.L + 1 - chrS, ex[ii].G - chrS);
+                junctions = true;
+            }
+            else if (gapG > 0) sink.op(gapG, CIG_D);
+        }
+        sink.op(ex[ii].L, CIG_M);
+    }
+    if (!junctions) sink.noJunction();
+    if (m.trimR1 > 0) sink.clip(m.trimR1, 1);
+}
+struct SamTextSink {                     // CIGAR, jM and jI of a mate as text, through pointers into the stack buffers of samMapped
+    char *c, *m, *q; const bool wantJ;   // jM / jI only when asked for
+    void op(uint64_t len, uint32_t code) { c = putUint(c, len); *c++ = CIG_LETTER[code]; }      // the text form carries the M of a zero-length block too (calcCIGAR.cpp:47)
+    void clip(uint64_t len, int) { op(len, CIG_S); }
+    void junction(int motif, uint64_t start, uint64_t end) { if (wantJ) { *m++ = ','; m = putInt(m, motif); *q++ = ','; q = putUint(q, start); *q++ = ','; q = putUint(q, end); } }
+    void noJunction() { if (wantJ) { m = putLit(m, ",-1"); q = putLit(q, ",-1"); } }
+};
+struct BamSink {                         // packed CIGAR of the record, calcCIGAR's text for the other mate's MC, junction arrays for jM / jI
+    std::string &cg; std::vector<uint32_t> &pc; std::vector<int32_t> &SJintron; std::vector<char> &SJmotif;
+    const int alignType; uint64_t *hardClip;
+    void text(uint64_t len, uint32_t code) { appendUint(cg, len); cg.push_back(CIG_LETTER[code]); }
+    void op(uint64_t len, uint32_t code) { text(len, code); if (code != CIG_M || len > 0) pc.push_back((uint32_t)len << 4 | code); }      // the packed form skips a zero-length block (alignBAM.cpp:260-261)
+    // BAM only: the clip at the chimeric junction of a supplementary record is a hard one: H in the record, still S in the text (alignBAM.cpp:237,273)
+    void clip(uint64_t len, int side) {
+        const bool hard = alignType == (side == 0 ? -11 : -12);
+        text(len, CIG_S);
+        pc.push_back((uint32_t)len << 4 | (hard ? CIG_H : CIG_S));
+        hardClip[side] = hard ? len : 0;
+    }
+    void junction(int motif, uint64_t start, uint64_t end) { SJmotif.push_back((char)motif); SJintron.push_back((int32_t)start); SJintron.push_back((int32_t)end); }
+    void noJunction() { SJmotif.push_back(-1); SJintron.push_back(-1); }
+};
+
+// NM and MD of a mate: the read in the orientation of the alignment against the genome text (outputTranscriptSAM.cpp:242-276, samAttrNM_MD alignBAM.cpp:9-45).
+// Mismatches and MD are the same in both; what a gap adds to NM is not:
+enum NmRule { NM_SAM,      // the deleted bases of a deletion (canonSJ -1), the inserted bases of an insertion (canonSJ -2)      (outputTranscriptSAM.cpp:263-272)
+              NM_BAM };    // the read gap of every gap and the genome gap of every gap that is no junction (canonSJ < 0)          (alignBAM.cpp:29-32)
+inline uint64_t tagsNMandMD(const GenomeIndex &gi, const ReadCtx &rc, const staramd_transcript &t, const staramd_exon *ex, const MateSpans::Span &m, NmRule rule, std::string &tagMD) {
+    const uint8_t *rd = rc.b->bases.data() + rc.b->readOffset[rc.i];
+    uint64_t tagNM = 0, matchN = 0;
+    for (uint32_t iex = m.iEx1; iex <= m.iEx2; iex++) {
+        for (uint32_t ii = 0; ii < ex[iex].L; ii++) {
+            uint64_t rp = (uint64_t)ex[iex].R + ii;
+            uint8_t r1 = t.roStr == 0 ? rd[rp] : rd[rc.Lread - 1 - rp];
+            if (t.roStr != 0 && r1 < 4) r1 = 3 - r1;
+            uint8_t g1 = gi.G[ex[iex].G + ii];
+            if (r1 != g1 || r1 == 4 || g1 == 4) { ++tagNM; appendUint(tagMD, matchN); tagMD.push_back("ACGTN"[g1 < 5 ? g1 : 4]); matchN = 0; }
+            else matchN++;
+        }
+        if (iex < m.iEx2) {
+            const uint64_t gapG = ex[iex + 1].G - (ex[iex].G + ex[iex].L), gapR = (uint64_t)ex[iex + 1].R - ex[iex].R - ex[iex].L;
+            if (rule == NM_BAM) tagNM += gapR + (ex[iex].canonSJ < 0 ? gapG : 0);
+            else tagNM += ex[iex].canonSJ == -1 ? gapG : ex[iex].canonSJ == -2 ? gapR : 0;
+            if (ex[iex].canonSJ == -1) {
+                appendUint(tagMD, matchN); tagMD.push_back('^');
+                for (uint64_t ii = ex[iex].G + ex[iex].L; ii < ex[iex + 1].G; ii++) { uint8_t g1 = gi.G[ii]; tagMD.push_back("ACGTN"[g1 < 5 ? g1 : 4]); }
+                matchN = 0;
+            }
+        }
+    }
+    appendUint(tagMD, matchN);
+    return tagNM;
+}
+
+// An unmapped mate (outputTranscriptSAM.cpp:11-40 = alignBAM.cpp:121-146): its flag and, when the other mate is mapped, where that one is
+struct UnmappedMate { uint32_t flag; bool mateMapped; uint32_t mateChr; uint64_t mateStart; };      // mateStart: 0-based in the chromosome
+inline UnmappedMate unmappedMate(const GenomeIndex &gi, const ReadCtx &rc, const staramd_transcript *trBest, const staramd_exon *exBest, int imate, const bool mateMap[2], bool mappedMateSecondary) {
+    UnmappedMate u{0x4, rc.nMates == 2 && mateMap[1 - imate], (uint32_t)-1, (uint64_t)-1};
+    if (rc.nMates == 2) {
+        u.flag |= 0x1 + (imate == 0 ? 0x40 : 0x80);
+        if (u.mateMapped) {
+            if (trBest->Str != (uint32_t)(1 - imate)) u.flag |= 0x20;
+            u.mateChr = trBest->Chr; u.mateStart = exBest[0].G - gi.chrStart[u.mateChr];
+            if (mappedMateSecondary) u.flag |= 0x100;        // KeepPairs: the unmapped mate of a secondary alignment is secondary too (:31-33, alignBAM.cpp:136-139)
+        } else u.flag |= 0x8;
+    }
+    if (rc.b->filter[rc.i] == 'Y') u.flag |= 0x200;
+    return u;
 }
 } // namespace
 
+// ---- ReadAlign::outputTranscriptSAM, mapped branch (:57-356) ----
 static void samMapped(std::string &out, const RunParams &P, const GenomeIndex &gi, const ReadCtx &rc, const TrView &tv, uint64_t nTrOut, uint64_t iTrOut, const ChimBam *chim = nullptr) {
     const staramd_transcript &t = *tv.t; const staramd_exon *ex = tv.ex;
     const ReadBatch &b = *rc.b; uint32_t ir = rc.i;
-    bool flagPaired = rc.nMates == 2;
-    uint32_t nEx = t.nExons;
-    uint32_t iExMate, nMates = 1;
-    for (iExMate = 0; iExMate + 1 < nEx; iExMate++) if (ex[iExMate].canonSJ == -3) { nMates = 2; break; }
-    uint32_t samFlagCommon = 0;
-    uint64_t Lread = rc.Lread;
-    if (flagPaired) {
-        samFlagCommon = 0x0001;
-        if (iExMate == nEx - 1) { if (!chim || chim->mateChr > gi.view.nChrReal) samFlagCommon += 0x0008; }      // no mate given: (uint)-1 > nChrReal (:75)
-        else if (P.dev.alignEndsProtrudeConcordantPair ||
-                 ((ex[0].G <= ex[iExMate + 1].G + ex[0].R) && (ex[iExMate].G + ex[iExMate].L <= ex[nEx - 1].G + Lread - ex[nEx - 1].R)))
-            samFlagCommon += 0x0002;
-    }
-    if (b.filter[ir] == 'Y') samFlagCommon += 0x200;
-    uint32_t Str = t.Str;
-    uint32_t leftMate = flagPaired ? Str : 0;
-    uint64_t chrS = gi.chrStart[t.Chr];
-    // the attributes of the run as codes (the list is a parameter: the same for every record)
-    // (decoded once per thread and run: eleven string compares per attribute and record were a tenth of the formatter's time)
-    static thread_local const RunParams *attrOf = nullptr; static thread_local SamAttr attr[32]; static thread_local uint32_t nAttr = 0; static thread_local bool wantJ = false;
-    static thread_local uint64_t attrKey = 0;
-    uint64_t key = P.outSAMattrOrder.size();                                  // the tags are two characters: a hash of them, not the address of P alone, says whether the list is the one decoded
-    for (const std::string &a : P.outSAMattrOrder) key = key * 1000003ull + (a.size() >= 2 ? (uint64_t)(uint8_t)a[0] * 257u + (uint8_t)a[1] : 0xFFFFu) + a.size();
-    if (attrOf != &P || attrKey != key) {
-        nAttr = 0; wantJ = false;
-        for (const std::string &a : P.outSAMattrOrder) { if (nAttr < 32) { attr[nAttr] = samAttrCode(a); wantJ = wantJ || attr[nAttr] == A_jM || attr[nAttr] == A_jI; nAttr++; } }
-        attrOf = &P; attrKey = key;
-    }
-    // ReadAlign::calcCIGAR (ReadAlign_calcCIGAR.cpp:3-58): the CIGAR of both mates first, the MC tag needs the other mate's.  At most 3 operations per exon + 2 clips,
-    // 21 characters each at the very most
+    const MateSpans ms = mateSpans(P, gi, rc, tv, nTrOut, chim);
+    const uint32_t nEx = t.nExons, Str = t.Str, nMates = ms.nMates, iExMate = ms.iExMate;
+    const uint64_t chrS = gi.chrStart[t.Chr], Lread = rc.Lread;
+    // SAM only: a pair is proper (0x2) if its ends do not protrude, or may (outputTranscriptSAM.cpp:79-83); alignBAM.cpp:191-192 sets the bit for every two-mate alignment
+    uint32_t flagProper = 0;
+    if (ms.flagPaired && nMates == 2 && (P.dev.alignEndsProtrudeConcordantPair ||
+                                         ((ex[0].G <= ex[iExMate + 1].G + ex[0].R) && (ex[iExMate].G + ex[iExMate].L <= ex[nEx - 1].G + Lread - ex[nEx - 1].R))))
+        flagProper = 0x0002;
+    // the CIGAR of both mates first, the MC tag needs the other mate's.  At most 3 operations per exon + 2 clips, 21 characters each at the very most
     char cig[2][(3 * STARAMD_MAX_N_EXONS + 2) * 21]; size_t cigLen[2] = {0, 0};
+    // jM / jI: at most one junction per exon, 4 + 2 x 21 characters each
+    char jm[2][STARAMD_MAX_N_EXONS * 5 + 8], ji[2][STARAMD_MAX_N_EXONS * 44 + 8]; size_t jmLen[2] = {0, 0}, jiLen[2] = {0, 0};
     for (uint32_t imate = 0; imate < nMates; imate++) {
-        uint32_t iEx1 = imate == 0 ? 0 : iExMate + 1, iEx2 = imate == 0 ? iExMate : nEx - 1;
-        uint32_t Mate = ex[iEx1].iFrag;
-        char *c = cig[imate];
-        const uint64_t trimL = rc.trimL(Str, Mate);
-        uint64_t trimL1 = trimL + ex[iEx1].R - (ex[iEx1].R < rc.readLength[leftMate] ? 0 : rc.readLength[leftMate] + 1);
-        if (trimL1 > 0) { c = putUint(c, trimL1); *c++ = 'S'; }
-        for (uint32_t ii = iEx1; ii <= iEx2; ii++) {
-            if (ii > iEx1) {
-                uint64_t gapG = ex[ii].G - (ex[ii - 1].G + ex[ii - 1].L);
-                uint64_t gapR = (uint64_t)ex[ii].R - ex[ii - 1].R - ex[ii - 1].L;
-                if (gapR > 0) { c = putUint(c, gapR); *c++ = 'I'; }
-                if (ex[ii - 1].canonSJ >= 0 || ex[ii - 1].sjAnnot == 1) { c = putUint(c, gapG); *c++ = 'N'; }
-                else if (gapG > 0) { c = putUint(c, gapG); *c++ = 'D'; }
-            }
-            c = putUint(c, ex[ii].L); *c++ = 'M';
-        }
-        uint64_t trimR1 = (ex[iEx1].R < rc.readLength[leftMate] ? rc.readLengthOriginal[leftMate] : rc.readLength[leftMate] + 1 + rc.readLengthOriginal[Mate])
-                          - ex[iEx2].R - ex[iEx2].L - trimL;
-        if (trimR1 > 0) { c = putUint(c, trimR1); *c++ = 'S'; }
-        cigLen[imate] = (size_t)(c - cig[imate]);
+        SamTextSink sink{cig[imate], jm[imate], ji[imate], P.attrWantJ};
+        walkMate(ex, ms.m[imate], chrS, sink);
+        cigLen[imate] = (size_t)(sink.c - cig[imate]); jmLen[imate] = (size_t)(sink.m - jm[imate]); jiLen[imate] = (size_t)(sink.q - ji[imate]);
     }
     for (uint32_t imate = 0; imate < nMates; imate++) {
-        uint32_t samFLAG = samFlagCommon;
-        uint32_t iEx1 = imate == 0 ? 0 : iExMate + 1, iEx2 = imate == 0 ? iExMate : nEx - 1;
-        uint32_t Mate = ex[iEx1].iFrag;
-        if (Mate == 0) { samFLAG |= Str * 0x10; if (nMates == 2) samFLAG |= (1 - Str) * 0x20; }
-        else { samFLAG |= (1 - Str) * 0x10; if (nMates == 2) samFLAG |= Str * 0x20; }
-        if (flagPaired) { samFLAG |= (Mate == 0 ? 0x0040 : 0x0080); if (nMates == 1 && chim && chim->mateStrand == 1) samFLAG |= 0x20; }     // :120-123
-        if (!tv.primary) samFLAG |= 0x100;
-        // jM / jI (only when asked for): at most one junction per exon, 4 + 2 x 21 characters each
-        char jm[STARAMD_MAX_N_EXONS * 5 + 8], ji[STARAMD_MAX_N_EXONS * 44 + 8]; size_t jmLen = 0, jiLen = 0;
-        if (wantJ) {
-            char *m = jm, *q = ji;
-            for (uint32_t ii = iEx1 + 1; ii <= iEx2; ii++) {
-                if (ex[ii - 1].canonSJ >= 0 || ex[ii - 1].sjAnnot == 1) {
-                    *m++ = ','; m = putInt(m, ex[ii - 1].canonSJ + (ex[ii - 1].sjAnnot == 0 ? 0 : 20));   // SJ_SAM_AnnotatedMotifShift
-                    *q++ = ','; q = putUint(q, ex[ii - 1].G + ex[ii - 1].L + 1 - chrS);
-                    *q++ = ','; q = putUint(q, ex[ii].G - chrS);
-                }
-            }
-            if (m == jm) { m = putLit(m, ",-1"); q = putLit(q, ",-1"); }
-            jmLen = (size_t)(m - jm); jiLen = (size_t)(q - ji);
-        }
-        // NM / MD (ReadAlign_outputTranscriptSAM.cpp:242-276): read in the orientation of the alignment against the genome text
+        const MateSpans::Span &m = ms.m[imate];
+        const uint32_t Mate = m.Mate, samFLAG = m.flag | flagProper;
         uint64_t tagNM = 0; std::string tagMD;
-        if (P.attrNMorMD) {
-            const uint8_t *rd = b.bases.data() + b.readOffset[ir];
-            uint64_t matchN = 0;
-            for (uint32_t iex = iEx1; iex <= iEx2; iex++) {
-                for (uint32_t ii = 0; ii < ex[iex].L; ii++) {
-                    uint64_t rp = (uint64_t)ex[iex].R + ii;
-                    uint8_t r1 = t.roStr == 0 ? rd[rp] : rd[Lread - 1 - rp];
-                    if (t.roStr != 0 && r1 < 4) r1 = 3 - r1;
-                    uint8_t g1 = gi.G[ex[iex].G + ii];
-                    if (r1 != g1 || r1 == 4 || g1 == 4) { ++tagNM; appendUint(tagMD, matchN); tagMD.push_back("ACGTN"[g1 < 5 ? g1 : 4]); matchN = 0; }
-                    else matchN++;
-                }
-                if (iex < iEx2) {
-                    if (ex[iex].canonSJ == -1) {
-                        tagNM += ex[iex + 1].G - (ex[iex].G + ex[iex].L);
-                        appendUint(tagMD, matchN); tagMD.push_back('^');
-                        for (uint64_t ii = ex[iex].G + ex[iex].L; ii < ex[iex + 1].G; ii++) { uint8_t g1 = gi.G[ii]; tagMD.push_back("ACGTN"[g1 < 5 ? g1 : 4]); }
-                        matchN = 0;
-                    } else if (ex[iex].canonSJ == -2) tagNM += (uint64_t)ex[iex + 1].R - ex[iex].R - ex[iex].L;
-                }
-            }
-            appendUint(tagMD, matchN);
-        }
-        int MAPQ = P.outSAMmapqUnique;
-        if (nTrOut >= 5) MAPQ = 0; else if (nTrOut >= 3) MAPQ = 1; else if (nTrOut == 2) MAPQ = 3;
+        if (P.attrNMorMD) tagNM = tagsNMandMD(gi, rc, t, ex, m, NM_SAM, tagMD);
+        // SAM input: its attributes go out again; indexed by the position of the mate in the alignment (outputTranscriptSAM.cpp:351-353), by the mate in BAM (alignBAM.cpp:485)
         const std::string_view nm = b.name(ir), sq = b.seq((int)Mate, ir), ql = b.qual((int)Mate, ir), xt = b.extra((int)imate, ir);
         const std::string &chrN = gi.chrName[t.Chr];
         const std::string *mateChrN = (nMates == 1 && chim && chim->mateChr < gi.view.nChrReal) ? &gi.chrName[chim->mateChr] : nullptr;
-        const std::string *rg = nullptr;
-        for (uint32_t k = 0; k < nAttr; k++) if (attr[k] == A_RG) rg = &P.outSAMattrRG.at(b.fileOf(ir));
+        const std::string *rg = P.attrHasRG ? &P.outSAMattrRG.at(b.fileOf(ir)) : nullptr;
+        const uint32_t nAttr = P.outSAMattrCodes.n;
         // upper bound of the line: the variable-length columns + 10 numbers of at most 21 characters + per attribute (a list may repeat an attribute) its tag,
         // a number and the longest variable-length payload an attribute can carry
-        const size_t attrVar = std::max(std::max((size_t)jmLen, (size_t)jiLen), std::max(std::max((size_t)cigLen[0], (size_t)cigLen[1]), std::max(tagMD.size(), rg ? rg->size() : (size_t)0)));
+        const size_t attrVar = std::max(std::max(jmLen[imate], jiLen[imate]), std::max(std::max(cigLen[0], cigLen[1]), std::max(tagMD.size(), rg ? rg->size() : (size_t)0)));
         const size_t bound = nm.size() + chrN.size() + (mateChrN ? mateChrN->size() : 0) + cigLen[0] + cigLen[1] + 2 * sq.size() + xt.size()
                              + 10 * 21 + (size_t)nAttr * (8 + 21 + attrVar) + 64;
         // the line is built in a buffer on the stack and appended once: growing `out` by the BOUND first (std::string::resize) zero-fills ~3x the bytes the line ends up with
@@ -243,17 +296,17 @@ static void samMapped(std::string &out, const RunParams &P, const GenomeIndex &g
         p = putSv(p, nm); *p++ = '\t';
         p = putUint(p, (samFLAG & P.outSAMflagAND) | P.outSAMflagOR); *p++ = '\t';
         p = putStr(p, chrN.data(), chrN.size()); *p++ = '\t';
-        p = putUint(p, ex[iEx1].G + 1 - chrS); *p++ = '\t';
-        p = putInt(p, MAPQ); *p++ = '\t';
+        p = putUint(p, ex[m.iEx1].G + 1 - chrS); *p++ = '\t';
+        p = putInt(p, ms.MAPQ); *p++ = '\t';
         p = putStr(p, cig[imate], cigLen[imate]);
         if (nMates > 1) {
-            p = putLit(p, "\t=\t"); p = putUint(p, ex[imate == 0 ? iExMate + 1 : 0].G + 1 - chrS); *p++ = '\t';
+            p = putLit(p, "\t=\t"); p = putUint(p, m.pnextG + 1 - chrS); *p++ = '\t';
             if (imate != 0) *p++ = '-';
-            p = putUint(p, ex[nEx - 1].G + ex[nEx - 1].L - ex[0].G);        // (--outSAMtlen 2 changes BAM output only, as in the reference)
+            p = putUint(p, ms.tlen);                                                // (--outSAMtlen 2 changes BAM output only, as in the reference: bamMapped)
         } else if (mateChrN) { *p++ = '\t'; p = putStr(p, mateChrN->data(), mateChrN->size()); *p++ = '\t'; p = putUint(p, (uint64_t)chim->mateStart + 1); p = putLit(p, "\t0"); }
         else p = putLit(p, "\t*\t0\t0");
         *p++ = '\t';
-        const bool noQS = P.outSAMmodeNoQS || b.fasta;           // readFileType==2 ? Qual : "*" (ReadAlign_outputTranscriptSAM.cpp:215)
+        const bool noQS = P.outSAMmodeNoQS || b.fasta;           // readFileType==2 && outSAMmode != "NoQS" ? Qual : "*" (outputTranscriptSAM.cpp:234)
         if (Mate == Str) { p = putSv(p, sq); *p++ = '\t'; if (!noQS) p = putSv(p, ql); else *p++ = '*'; }
         else {
             const size_t n = sq.size();
@@ -261,23 +314,22 @@ static void samMapped(std::string &out, const RunParams &P, const GenomeIndex &g
             p += n; *p++ = '\t';
             if (!noQS) { revCopy(p, ql.data(), n); p += n; } else *p++ = '*';
         }
-        for (uint32_t k = 0; k < nAttr; k++) {
-            switch (attr[k]) {
-                case A_NH: p = putLit(p, "\tNH:i:"); p = putUint(p, nTrOut); break;
-                case A_HI: p = putLit(p, "\tHI:i:"); p = putInt(p, (int64_t)iTrOut + P.outSAMattrIHstart); break;
-                case A_AS: p = putLit(p, "\tAS:i:"); p = putInt(p, t.maxScore); break;
-                case A_nM: p = putLit(p, "\tnM:i:"); p = putUint(p, t.nMM); break;
-                case A_jM: p = putLit(p, "\tjM:B:c"); p = putStr(p, jm, jmLen); break;
-                case A_jI: p = putLit(p, "\tjI:B:i"); p = putStr(p, ji, jiLen); break;
-                case A_XS: if (t.sjMotifStrand == 1) p = putLit(p, "\tXS:A:+"); else if (t.sjMotifStrand == 2) p = putLit(p, "\tXS:A:-"); break;
-                case A_NM: p = putLit(p, "\tNM:i:"); p = putUint(p, tagNM); break;
-                case A_MD: p = putLit(p, "\tMD:Z:"); p = putStr(p, tagMD.data(), tagMD.size()); break;
-                case A_MC: if (nMates > 1) { p = putLit(p, "\tMC:Z:"); p = putStr(p, cig[1 - imate], cigLen[1 - imate]); } break;
-                case A_RG: p = putLit(p, "\tRG:Z:"); p = putStr(p, rg->data(), rg->size()); break;
-                default: break;
+        for (const SamAttr a : P.outSAMattrCodes) {
+            switch (a) {
+                case SamAttr::NH: p = putLit(p, "\tNH:i:"); p = putUint(p, nTrOut); break;
+                case SamAttr::HI: p = putLit(p, "\tHI:i:"); p = putInt(p, (int64_t)iTrOut + P.outSAMattrIHstart); break;
+                case SamAttr::AS: p = putLit(p, "\tAS:i:"); p = putInt(p, t.maxScore); break;
+                case SamAttr::nM: p = putLit(p, "\tnM:i:"); p = putUint(p, t.nMM); break;
+                case SamAttr::jM: p = putLit(p, "\tjM:B:c"); p = putStr(p, jm[imate], jmLen[imate]); break;
+                case SamAttr::jI: p = putLit(p, "\tjI:B:i"); p = putStr(p, ji[imate], jiLen[imate]); break;
+                case SamAttr::XS: if (t.sjMotifStrand == 1) p = putLit(p, "\tXS:A:+"); else if (t.sjMotifStrand == 2) p = putLit(p, "\tXS:A:-"); break;
+                case SamAttr::NM: p = putLit(p, "\tNM:i:"); p = putUint(p, tagNM); break;
+                case SamAttr::MD: p = putLit(p, "\tMD:Z:"); p = putStr(p, tagMD.data(), tagMD.size()); break;
+                case SamAttr::MC: if (nMates > 1) { p = putLit(p, "\tMC:Z:"); p = putStr(p, cig[1 - imate], cigLen[1 - imate]); } break;
+                case SamAttr::RG: p = putLit(p, "\tRG:Z:"); p = putStr(p, rg->data(), rg->size()); break;
+                case SamAttr::ch: case SamAttr::vA: case SamAttr::vG: case SamAttr::vW: case SamAttr::rB: case SamAttr::cN: case SamAttr::OTHER: break;     // BAM only: skipped without a word (outputTranscriptSAM.cpp:326-343; cN, which only Chimeric.out.sam beside a BAM can bring here, the reference refuses)
             }
         }
-        // SAM input: its attributes go out again; indexed by the position of the mate in the alignment, not by the mate, as the reference does (:351-353)
         if (!xt.empty()) { *p++ = '\t'; p = putSv(p, xt); }
         *p++ = '\n';
         if (onStack) out.append(lineBuf, (size_t)(p - p0)); else out.resize(base + (size_t)(p - p0));
@@ -338,6 +390,13 @@ void attrFromSAMtags(std::string &a, std::string_view tags, const RunParams &P) 
         }
     } while (pos2 != std::string_view::npos);
 }
+// BAM B-array attribute: tag, element type, count, elements
+template <class T> void attrArray(std::string &a, const char *tagAndType, const T *v, size_t n) {
+    const uint32_t n32 = (uint32_t)n;
+    a.append(tagAndType, 2); a.push_back('B'); a.push_back(tagAndType[2]); a.append((const char *)&n32, 4); a.append((const char *)v, sizeof(T) * n);
+}
+// cN: bases clipped from the 5' and the 3' end (alignBAM.cpp:181-184 unmapped, :318-322 mapped: indexed by the position of the mate in the alignment, not by the mate)
+void attrCN(std::string &a, const ReadCtx &rc, uint32_t imate) { const int32_t v1[2] = {(int32_t)rc.clip[imate][0], (int32_t)rc.clip[imate][1]}; attrArray(a, "cNi", v1, 2); }
 // tail of a record: name, CIGAR, packed sequence, qualities, attributes (:547-590); the 9 core words come first
 void bamFinish(std::string &out, const uint32_t core[8], std::string_view name, const std::vector<uint32_t> &cigar, std::string_view seq, std::string_view qual, bool rev,
                bool noQS, const std::string &attr, size_t hardL = 0, size_t hardR = 0) {
@@ -359,137 +418,77 @@ void bamFinish(std::string &out, const uint32_t core[8], std::string_view name, 
 } // namespace
 
 // mapped mates of one alignment (alignType -1)
-// quant = a projection onto a transcript (ReadAlign_quantTranscriptome.cpp:71-76): coordinates start at 0, attributes NH HI (+ RG, MC)
+// quant = a projection onto a transcript (ReadAlign_quantTranscriptome.cpp:71-76): coordinates start at 0 (chrS = 0), the attributes are the quant list
+// (NH HI + RG, MC, ...), and no NM / MD
 static void bamMapped(std::string &out, const RunParams &P, const GenomeIndex &gi, const ReadCtx &rc, const TrView &tv, uint64_t nTrOut, uint64_t iTrOut, std::vector<BamKey> *keys,
                       bool quant = false, std::vector<uint64_t> *recOffsets = nullptr, const ChimBam *chim = nullptr) {
     const int alignType = chim ? chim->alignType : -1;
     const uint32_t mateChr = chim ? chim->mateChr : (uint32_t)-1;
     const staramd_transcript &t = *tv.t; const staramd_exon *ex = tv.ex;
     const ReadBatch &b = *rc.b; uint32_t ir = rc.i;
-    const bool flagPaired = rc.nMates == 2;
-    const uint32_t nEx = t.nExons;
-    uint32_t iExMate, nMates = 1;
-    for (iExMate = 0; iExMate + 1 < nEx; iExMate++) if (ex[iExMate].canonSJ == -3) { nMates = 2; break; }
-    const uint32_t Str = t.Str, leftMate = flagPaired ? Str : 0;
+    const MateSpans ms = mateSpans(P, gi, rc, tv, nTrOut, chim);
+    const uint32_t nEx = t.nExons, Str = t.Str, nMates = ms.nMates, iExMate = ms.iExMate;
     const uint64_t chrS = quant ? 0 : gi.chrStart[t.Chr], Lread = rc.Lread;
+    // BAM only: every two-mate alignment is a proper pair (alignBAM.cpp:191-192; SAM asks more, see samMapped), 0x800 marks supplementary chimeric segments (:200)
+    const uint32_t flagBam = (ms.flagPaired && nMates == 2 ? 0x0002 : 0) | (alignType == -11 || alignType == -12 || alignType == -13 ? 0x800 : 0);
     // CIGAR strings of both mates for MC (calcCIGAR)
     std::string matesCIGAR[2];
     std::vector<uint32_t> packed[2]; std::vector<int32_t> SJintron[2]; std::vector<char> SJmotif[2];
     VarOverlap vo; bool varDone = false;
-    uint64_t hardClip[2][2];
+    uint64_t hardClip[2][2] = {{0, 0}, {0, 0}};
     for (uint32_t imate = 0; imate < nMates; imate++) {
-        uint32_t iEx1 = imate == 0 ? 0 : iExMate + 1, iEx2 = imate == 0 ? iExMate : nEx - 1;
-        uint32_t Mate = ex[iEx1].iFrag;
-        std::string &cg = matesCIGAR[imate]; std::vector<uint32_t> &pc = packed[imate];
-        auto op = [&](uint64_t len, char c, uint32_t code, bool inString) { pc.push_back((uint32_t)len << 4 | code); if (inString) { appendUint(cg, len); cg.push_back(c); } };
-        const uint64_t trimL = rc.trimL(Str, Mate);
-        uint64_t trimL1 = trimL + ex[iEx1].R - (ex[iEx1].R < rc.readLength[leftMate] ? 0 : rc.readLength[leftMate] + 1);
-        hardClip[imate][0] = hardClip[imate][1] = 0;
-        if (trimL1 > 0) { op(trimL1, 'S', 4, true); if (alignType == -11) { pc.back() = (uint32_t)trimL1 << 4 | 5; hardClip[imate][0] = trimL1; } }     // H in the record, S in the MC string of calcCIGAR
-        for (uint32_t ii = iEx1; ii <= iEx2; ii++) {
-            if (ii > iEx1) {
-                uint64_t gapG = ex[ii].G - (ex[ii - 1].G + ex[ii - 1].L);
-                uint64_t gapR = (uint64_t)ex[ii].R - ex[ii - 1].R - ex[ii - 1].L;
-                if (gapR > 0) op(gapR, 'I', 1, true);
-                if (ex[ii - 1].canonSJ >= 0 || ex[ii - 1].sjAnnot == 1) {
-                    op(gapG, 'N', 3, true);
-                    SJmotif[imate].push_back((char)(ex[ii - 1].canonSJ + (ex[ii - 1].sjAnnot == 0 ? 0 : 20)));
-                    SJintron[imate].push_back((int32_t)(ex[ii - 1].G + ex[ii - 1].L + 1 - chrS)); SJintron[imate].push_back((int32_t)(ex[ii].G - chrS));
-                } else if (gapG > 0) op(gapG, 'D', 2, true);
-            }
-            // the CIGAR string of calcCIGAR always has the M; the packed one skips 0-length blocks (:223-224)
-            appendUint(cg, ex[ii].L); cg.push_back('M');
-            if (ex[ii].L > 0) pc.push_back((uint32_t)ex[ii].L << 4 | 0);
-        }
-        if (SJmotif[imate].empty()) { SJmotif[imate].push_back(-1); SJintron[imate].push_back(-1); }
-        uint64_t trimR1 = (ex[iEx1].R < rc.readLength[leftMate] ? rc.readLengthOriginal[leftMate] : rc.readLength[leftMate] + 1 + rc.readLengthOriginal[Mate]) - ex[iEx2].R - ex[iEx2].L - trimL;
-        if (trimR1 > 0) { op(trimR1, 'S', 4, true); if (alignType == -12) { pc.back() = (uint32_t)trimR1 << 4 | 5; hardClip[imate][1] = trimR1; } }
+        BamSink sink{matesCIGAR[imate], packed[imate], SJintron[imate], SJmotif[imate], alignType, hardClip[imate]};
+        walkMate(ex, ms.m[imate], chrS, sink);
     }
     for (uint32_t imate = 0; imate < nMates; imate++) {
-        uint32_t iEx1 = imate == 0 ? 0 : iExMate + 1, iEx2 = imate == 0 ? iExMate : nEx - 1;
-        uint32_t Mate = ex[iEx1].iFrag;
-        uint32_t samFLAG = 0;
-        if (flagPaired) { samFLAG = 0x0001; if (iExMate == nEx - 1) { if (mateChr > gi.view.nChrReal) samFLAG |= 0x0008; } else samFLAG |= 0x0002; }     // without a chimeric mate: (uint)-1 > nChrReal
-        if (b.filter[ir] == 'Y') samFLAG |= 0x200;
-        if (alignType == -11 || alignType == -12 || alignType == -13) samFLAG |= 0x800;
-        if (!tv.primary) samFLAG |= 0x100;
-        if (Mate == 0) { samFLAG |= Str * 0x10; if (nMates == 2) samFLAG |= (1 - Str) * 0x20; }
-        else { samFLAG |= (1 - Str) * 0x10; if (nMates == 2) samFLAG |= Str * 0x20; }
-        if (flagPaired) { samFLAG |= (Mate == 0 ? 0x0040 : 0x0080); if (nMates == 1 && chim && chim->mateStrand == 1) samFLAG |= 0x20; }
-        int MAPQ = P.outSAMmapqUnique;
-        if (nTrOut >= 5) MAPQ = 0; else if (nTrOut >= 3) MAPQ = 1; else if (nTrOut == 2) MAPQ = 3;
-        // NM / MD of the BAM path (samAttrNM_MD :8-47): insertions of every gap and deletions of every non-junction gap count
+        const MateSpans::Span &m = ms.m[imate];
+        const uint32_t iEx1 = m.iEx1, iEx2 = m.iEx2, Mate = m.Mate, samFLAG = m.flag | flagBam;
         uint64_t tagNM = 0; std::string tagMD;
-        if (P.attrNMorMD && !quant) {
-            const uint8_t *rd = b.bases.data() + b.readOffset[ir];
-            uint64_t matchN = 0, nMM = 0, nI = 0, nD = 0;
-            for (uint32_t iex = iEx1; iex <= iEx2; iex++) {
-                for (uint32_t ii = 0; ii < ex[iex].L; ii++) {
-                    uint64_t rp = (uint64_t)ex[iex].R + ii;
-                    uint8_t r1 = t.roStr == 0 ? rd[rp] : rd[Lread - 1 - rp];
-                    if (t.roStr != 0 && r1 < 4) r1 = 3 - r1;
-                    uint8_t g1 = gi.G[ex[iex].G + ii];
-                    if (r1 != g1 || r1 == 4 || g1 == 4) { ++nMM; appendUint(tagMD, matchN); tagMD.push_back("ACGTN"[g1 < 5 ? g1 : 4]); matchN = 0; }
-                    else matchN++;
-                }
-                if (iex < iEx2) {
-                    if (ex[iex].canonSJ < 0) nD += ex[iex + 1].G - (ex[iex].G + ex[iex].L);
-                    nI += (uint64_t)ex[iex + 1].R - ex[iex].R - ex[iex].L;
-                    if (ex[iex].canonSJ == -1) {
-                        appendUint(tagMD, matchN); tagMD.push_back('^');
-                        for (uint64_t ii = ex[iex].G + ex[iex].L; ii < ex[iex + 1].G; ii++) { uint8_t g1 = gi.G[ii]; tagMD.push_back("ACGTN"[g1 < 5 ? g1 : 4]); }
-                        matchN = 0;
-                    }
-                }
-            }
-            appendUint(tagMD, matchN);
-            tagNM = nMM + nI + nD;
-        }
+        if (P.attrNMorMD && !quant) tagNM = tagsNMandMD(gi, rc, t, ex, m, NM_BAM, tagMD);
         std::string attr;
-        for (const std::string &a : (quant ? P.outSAMattrOrderQuant : P.outSAMattrOrder)) {
-            if (a == "NH") attrInt(attr, "NH", (int64_t)nTrOut);
-            else if (a == "HI") attrInt(attr, "HI", (int64_t)iTrOut + P.outSAMattrIHstart);
-            else if (a == "AS") attrInt(attr, "AS", t.maxScore);
-            else if (a == "nM") attrInt(attr, "nM", t.nMM);
-            else if (a == "jM") { attr += "jMBc"; uint32_t n = (uint32_t)SJmotif[imate].size(); attr.append((const char *)&n, 4); attr.append(SJmotif[imate].data(), n); }
-            else if (a == "jI") { attr += "jIBi"; uint32_t n = (uint32_t)SJintron[imate].size(); attr.append((const char *)&n, 4); attr.append((const char *)SJintron[imate].data(), 4 * (size_t)n); }
-            else if (a == "XS") { if (t.sjMotifStrand == 1) attrChar(attr, "XS", '+'); else if (t.sjMotifStrand == 2) attrChar(attr, "XS", '-'); }
-            else if (a == "NM") attrInt(attr, "NM", (int64_t)tagNM);
-            else if (a == "MD") attrStr(attr, "MD", tagMD);
-            else if (a == "MC") { if (nMates > 1) attrStr(attr, "MC", matesCIGAR[1 - imate]); }
-            else if (a == "RG") attrStr(attr, "RG", P.outSAMattrRG.at(b.fileOf(ir)));
-            else if (a == "ch") { if (alignType <= -10) attrChar(attr, "ch", '1'); }
-            else if ((a == "vA" || a == "vG") && P.var) {          // ReadAlign_alignBAM.cpp:347-360: the SNVs under the whole alignment, on every record of it
-                if (!varDone && chim && chim->var) { vo = *chim->var; varDone = true; }
-                if (!varDone) { P.var->overlap(t, ex, b.bases.data() + b.readOffset[ir], Lread, quant ? 0 : gi.chrStart[t.Chr], vo); varDone = true; }
-                if (!vo.allele.empty()) {
-                    uint32_t nv = (uint32_t)vo.allele.size();
-                    if (a == "vA") { attr += "vABc"; attr.append((const char *)&nv, 4); attr.append(vo.allele.data(), nv); }
-                    else { attr += "vGBi"; attr.append((const char *)&nv, 4); attr.append((const char *)vo.genCoord.data(), 4 * (size_t)nv); }
+        for (const SamAttr a : (quant ? P.outSAMattrCodesQuant : P.outSAMattrCodes)) {
+            switch (a) {
+                case SamAttr::NH: attrInt(attr, "NH", (int64_t)nTrOut); break;
+                case SamAttr::HI: attrInt(attr, "HI", (int64_t)iTrOut + P.outSAMattrIHstart); break;
+                case SamAttr::AS: attrInt(attr, "AS", t.maxScore); break;
+                case SamAttr::nM: attrInt(attr, "nM", t.nMM); break;
+                case SamAttr::jM: attrArray(attr, "jMc", SJmotif[imate].data(), SJmotif[imate].size()); break;
+                case SamAttr::jI: attrArray(attr, "jIi", SJintron[imate].data(), SJintron[imate].size()); break;
+                case SamAttr::XS: if (t.sjMotifStrand == 1) attrChar(attr, "XS", '+'); else if (t.sjMotifStrand == 2) attrChar(attr, "XS", '-'); break;
+                case SamAttr::NM: attrInt(attr, "NM", (int64_t)tagNM); break;
+                case SamAttr::MD: attrStr(attr, "MD", tagMD); break;
+                case SamAttr::MC: if (nMates > 1) attrStr(attr, "MC", matesCIGAR[1 - imate]); break;
+                case SamAttr::RG: attrStr(attr, "RG", P.outSAMattrRG.at(b.fileOf(ir))); break;
+                // ---- the attributes below are BAM only
+                case SamAttr::ch: if (alignType <= -10) attrChar(attr, "ch", '1'); break;
+                case SamAttr::vA: case SamAttr::vG:                                 // alignBAM.cpp:347-360: the SNVs under the whole alignment, on every record of it
+                    if (!P.var) break;
+                    if (!varDone && chim && chim->var) { vo = *chim->var; varDone = true; }
+                    if (!varDone) { P.var->overlap(t, ex, b.bases.data() + b.readOffset[ir], Lread, quant ? 0 : gi.chrStart[t.Chr], vo); varDone = true; }
+                    if (!vo.allele.empty()) { if (a == SamAttr::vA) attrArray(attr, "vAc", vo.allele.data(), vo.allele.size()); else attrArray(attr, "vGi", vo.genCoord.data(), vo.allele.size()); }
+                    break;
+                case SamAttr::vW: if (rc.waspType != -1) { int32_t w = rc.waspType; attr += "vWi"; attr.append((const char *)&w, 4); } break;
+                case SamAttr::rB: {                                          // :335-346 read and genome coordinates of every block of this mate
+                    std::vector<int32_t> rb;
+                    for (uint32_t ii = iEx1; ii <= iEx2; ii++) { rb.push_back((int32_t)ex[ii].R + 1); rb.push_back((int32_t)ex[ii].R + ex[ii].L); rb.push_back((int32_t)(ex[ii].G - chrS + 1)); rb.push_back((int32_t)(ex[ii].G - chrS + ex[ii].L)); }
+                    attrArray(attr, "rBi", rb.data(), rb.size());
+                    break;
                 }
+                case SamAttr::cN: attrCN(attr, rc, imate); break;
+                case SamAttr::OTHER: break;
             }
-            else if (a == "rB") {                                  // :335-346 read and genome coordinates of every block of this mate
-                std::vector<int32_t> rb;
-                for (uint32_t ii = iEx1; ii <= iEx2; ii++) { rb.push_back((int32_t)ex[ii].R + 1); rb.push_back((int32_t)ex[ii].R + ex[ii].L); rb.push_back((int32_t)(ex[ii].G - chrS + 1)); rb.push_back((int32_t)(ex[ii].G - chrS + ex[ii].L)); }
-                attr += "rBBi"; uint32_t n = (uint32_t)rb.size(); attr.append((const char *)&n, 4); attr.append((const char *)rb.data(), 4 * (size_t)n);
-            }
-            else if (a == "cN") {                                  // :318-322 clipped bases at the 5' and 3' end; indexed by the position of the mate in the alignment, as in the reference
-                int32_t v1[2] = {(int32_t)rc.clip[imate][0], (int32_t)rc.clip[imate][1]};
-                attr += "cNBi"; uint32_t n = 2; attr.append((const char *)&n, 4); attr.append((const char *)v1, 8);
-            }
-            else if (a == "vW") { if (rc.waspType != -1) { int32_t w = rc.waspType; attr += "vWi"; attr.append((const char *)&w, 4); } }
         }
-        attrFromSAMtags(attr, b.extra((int)Mate, ir), P);
+        attrFromSAMtags(attr, b.extra((int)Mate, ir), P);             // SAM input: by the mate (alignBAM.cpp:485), not by its position in the alignment as in SAM
         uint32_t core[8];
         core[0] = t.Chr;
         core[1] = (uint32_t)(ex[iEx1].G - chrS);
-        core[2] = ((uint32_t)reg2bin((int)(ex[iEx1].G - chrS), (int)(ex[iEx2].G + ex[iEx2].L - chrS)) << 16) | ((uint32_t)MAPQ << 8) | (uint32_t)(b.name(ir).size() + 1);
+        core[2] = ((uint32_t)reg2bin((int)(ex[iEx1].G - chrS), (int)(ex[iEx2].G + ex[iEx2].L - chrS)) << 16) | ((uint32_t)ms.MAPQ << 8) | (uint32_t)(b.name(ir).size() + 1);
         core[3] = (((samFLAG & P.outSAMflagAND) | P.outSAMflagOR) << 16) | (uint32_t)packed[imate].size();
         core[4] = (uint32_t)(b.seq((int)Mate, ir).size() - hardClip[imate][0] - hardClip[imate][1]);
         if (nMates > 1) {
-            core[5] = t.Chr; core[6] = (uint32_t)(ex[imate == 0 ? iExMate + 1 : 0].G - chrS);
-            int32_t tlen = (int32_t)(ex[nEx - 1].G + ex[nEx - 1].L - ex[0].G);                 // outSAMtlen 1
-            if (P.outSAMtlen == 2) {                                                             // :78-82: leftmost base of any mate to rightmost base of any mate
+            core[5] = t.Chr; core[6] = (uint32_t)(m.pnextG - chrS);
+            int32_t tlen = (int32_t)ms.tlen;
+            if (P.outSAMtlen == 2) {           // BAM only (alignBAM.cpp:84-88,566-574): leftmost base of any mate to rightmost base of any mate, + for the mate that has the leftmost
                 tlen = (int32_t)(std::max(ex[nEx - 1].G + ex[nEx - 1].L, ex[iExMate].G + ex[iExMate].L) - std::min(ex[0].G, ex[iExMate + 1].G));
                 core[7] = (uint32_t)(imate == (ex[0].G <= ex[iExMate + 1].G ? 0u : 1u) ? tlen : -tlen);
             } else core[7] = (uint32_t)(imate == 0 ? tlen : -tlen);
@@ -624,30 +623,22 @@ static void bamUnmapped(std::string &out, const RunParams &P, const GenomeIndex 
     const ReadBatch &b = *rc.b; uint32_t ir = rc.i;
     for (int imate = 0; imate < rc.nMates; imate++) {
         if (mateMap[imate]) continue;
-        uint32_t samFLAG = 0x4; uint32_t mateChr = (uint32_t)-1, mateStart = (uint32_t)-1;
-        if (rc.nMates == 2) {
-            samFLAG |= 0x1 + (imate == 0 ? 0x40 : 0x80);
-            if (mateMap[1 - imate]) {
-                if (trBest->Str != (uint32_t)(1 - imate)) samFLAG |= 0x20;
-                mateChr = trBest->Chr; mateStart = (uint32_t)(exBest[0].G - gi.chrStart[mateChr]);
-                if (mappedMateSecondary) samFLAG |= 0x100;       // KeepPairs: the unmapped mate of a secondary alignment is secondary too (:136-139)
-            } else samFLAG |= 0x8;
-        }
-        if (b.filter[ir] == 'Y') samFLAG |= 0x200;
+        const UnmappedMate u = unmappedMate(gi, rc, trBest, exBest, imate, mateMap, mappedMateSecondary);
         std::string attr;
         attrInt(attr, "NH", 0); attrInt(attr, "HI", 0); attrInt(attr, "AS", trBest ? trBest->maxScore : 0); attrInt(attr, "nM", trBest ? trBest->nMM : 0);
         attrChar(attr, "uT", (char)('0' + unmapType));
         if (!P.outSAMattrRG.empty()) attrStr(attr, "RG", P.outSAMattrRG.at(b.fileOf(ir)));
-        if (std::find(P.outSAMattrOrder.begin(), P.outSAMattrOrder.end(), "cN") != P.outSAMattrOrder.end()) { int32_t v1[2] = {(int32_t)rc.clip[imate][0], (int32_t)rc.clip[imate][1]}; attr += "cNBi"; uint32_t n = 2; attr.append((const char *)&n, 4); attr.append((const char *)v1, 8); }   // :181-184
+        if (P.attrHasCN) attrCN(attr, rc, (uint32_t)imate);                // BAM only (:181-184); the unmapped SAM record has no such column
         attrFromSAMtags(attr, b.extra(imate, ir), P);
         uint32_t core[8];
         core[0] = (uint32_t)-1; core[1] = (uint32_t)-1;
         core[2] = ((uint32_t)reg2bin(-1, 0) << 16) | (uint32_t)(b.name(ir).size() + 1);
-        core[3] = (((samFLAG & P.outSAMflagAND) | P.outSAMflagOR) << 16);
+        core[3] = (((u.flag & P.outSAMflagAND) | P.outSAMflagOR) << 16);
         core[4] = (uint32_t)b.seq(imate, ir).size();
-        if (mateChr < gi.view.nChrReal) { core[5] = mateChr; core[6] = mateStart; } else { core[5] = (uint32_t)-1; core[6] = (uint32_t)-1; }
+        if (u.mateChr < gi.view.nChrReal) { core[5] = u.mateChr; core[6] = (uint32_t)u.mateStart; } else { core[5] = (uint32_t)-1; core[6] = (uint32_t)-1; }
         core[7] = 0;
         const size_t off0 = out.size();
+        // qualities: "*" (0xFF) for FASTA input and for --outSAMmode NoQS (alignBAM.cpp:594); the unmapped SAM record looks at the input alone, see samUnmapped
         bamFinish(out, core, b.name(ir), std::vector<uint32_t>(), b.seq(imate, ir), b.qual(imate, ir), false, P.outSAMmodeNoQS || b.fasta, attr);
         if (keys) keys->push_back(BamKey{~0ull, b.readIndex(ir) << 32, off0, (uint32_t)(out.size() - off0), 0});      // unmapped: last, in read order
     }
@@ -678,18 +669,12 @@ static void samUnmapped(std::string &out, const RunParams &P, const GenomeIndex 
     const ReadBatch &b = *rc.b; uint32_t ir = rc.i;
     for (int imate = 0; imate < rc.nMates; imate++) {
         if (mateMap[imate]) continue;
-        uint32_t samFLAG = 0x4;
-        if (rc.nMates == 2) {
-            samFLAG |= 0x1 + (imate == 0 ? 0x40 : 0x80);
-            if (mateMap[1 - imate]) { if (trBest->Str != (uint32_t)(1 - imate)) samFLAG |= 0x20; }
-            else samFLAG |= 0x8;
-        }
-        if (b.filter[ir] == 'Y') samFLAG |= 0x200;
-        if (rc.nMates == 2 && mateMap[1 - imate] && mappedMateSecondary) samFLAG |= 0x100;      // :31-33 (KeepPairs)
-        out += b.name(ir); out.push_back('\t'); appendUint(out, samFLAG); out += "\t*\t0\t0\t*";
-        if (rc.nMates == 2 && mateMap[1 - imate]) { out.push_back('\t'); out += gi.chrName[trBest->Chr]; out.push_back('\t'); appendUint(out, exBest[0].G + 1 - gi.chrStart[trBest->Chr]); }
+        const UnmappedMate u = unmappedMate(gi, rc, trBest, exBest, imate, mateMap, mappedMateSecondary);
+        out += b.name(ir); out.push_back('\t'); appendUint(out, u.flag); out += "\t*\t0\t0\t*";
+        if (u.mateMapped) { out.push_back('\t'); out += gi.chrName[u.mateChr]; out.push_back('\t'); appendUint(out, u.mateStart + 1); }
         else out += "\t*\t0";
-        out += "\t0\t"; out += b.seq(imate, ir); out.push_back('\t'); if (b.fasta) out.push_back('*'); else out += b.qual(imate, ir);      // :44
+        // SAM only: qualities are "*" for FASTA input alone, --outSAMmode NoQS is not looked at here (outputTranscriptSAM.cpp:43; the mapped branch :234 and alignBAM.cpp:594 do)
+        out += "\t0\t"; out += b.seq(imate, ir); out.push_back('\t'); if (b.fasta) out.push_back('*'); else out += b.qual(imate, ir);
         out += "\tNH:i:0\tHI:i:0\tAS:i:"; appendInt(out, trBest ? trBest->maxScore : 0);
         out += "\tnM:i:"; appendUint(out, trBest ? trBest->nMM : 0); out += "\tuT:A:"; appendInt(out, unmapType);
         if (!P.outSAMattrRG.empty()) { out += "\tRG:Z:"; out += P.outSAMattrRG.at(b.fileOf(ir)); }
@@ -1042,7 +1027,6 @@ std::string PostMap::processRange(const ReadBatch &b, const staramd_results &r, 
             recordSJ(P, trMult, nTr, sj);
             if (gc && nTr > 0) gc->addAlign(*genes, nTr, *trMult[0].t, trMult[0].ex);        // alignedAnnotation (ReadAlign_outputAlignments.cpp:298-308)
             if (quantBam) quantTranscriptome(P, gi, rc, *transcripts, trMult, nTr, b.mmMaxTotal[ir], *quantBam, *quantPatches);
-            // writeSAM (:132-256), default outSAMmultNmax=-1: all nTr
             // writeSAM (:132-256): at most --outSAMmultNmax alignments are written (NH keeps the full count)
             const uint64_t nTrWrite = P.outSAMmultNmax < 0 ? nTr : std::min<uint64_t>(nTr, (uint64_t)P.outSAMmultNmax);
             const bool keepPairs = P.outSAMunmappedKeepPairs;

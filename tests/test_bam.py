@@ -12,7 +12,10 @@ CASES = [("pe101", []),
          ("se50", ["--outSAMunmapped", "Within"]),
          ("pe150_indel", ["--outSAMattributes", "NH", "HI", "AS", "nM", "NM", "MD", "jM", "jI", "MC", "XS", "--outSAMunmapped", "Within", "--outSAMstrandField", "intronMotif"]),
          ("pe150_chim", ["--outSAMattributes", "All", "--outSAMunmapped", "Within", "--runThreadN", "3", "--outBAMcompression", "6"]),
-         ("pe76_overlap", ["--twopassMode", "Basic"])]
+         ("pe76_overlap", ["--twopassMode", "Basic"]),
+         # pairs whose ends protrude are allowed but not concordant: proper-pair bit 0x2 in every two-mate BAM record all the same, and TLEN from the leftmost to
+         # the rightmost base of either mate (SAM: test_clipping.py "protrude")
+         ("pe76_overlap", ["--alignEndsProtrude", "10", "DiscordantPair", "--clip5pNbases", "6", "3", "--outSAMtlen", "2"])]
 
 
 def _case(name, more, tmp_path, factory):

@@ -53,6 +53,9 @@ PE = {
     "one_mate": ["--clip3pAdapterSeq", "-", AD2, "--clip3pAdapterMMp", "0.1", "0.1", "--clip5pNbases", "6", "0", "--clip5pAfterAdapterNbases", "2", "9"],
     "polyA": ["--clip3pAdapterSeq", "polyA", "-", "--clip3pAdapterMMp", "0.1", "0.1", "--outSAMunmapped", "Within"],
 }
+# short inserts (pe76_overlap): 5' clips let the second mate start before the first.  Such a pair is aligned, in SAM without the proper-pair bit 0x2 and with the
+# TLEN of --outSAMtlen 1 whatever that option says (in BAM with the bit and with the other TLEN: test_bam.py)
+PROTRUDE = ["--alignEndsProtrude", "10", "DiscordantPair", "--clip5pNbases", "6", "3", "--outSAMtlen", "2"]
 SE = {
     "n5n3": ["--clip5pNbases", "5", "--clip3pNbases", "9"],
     "adapter": ["--clip3pAdapterSeq", AD1, "--outSAMunmapped", "Within", "--clip3pAfterAdapterNbases", "1"],
@@ -70,10 +73,10 @@ def _run(info, tag, flags, tmp_path, adapters=None, zero_len=True, **kw):
     return ref, new
 
 
-@pytest.mark.parametrize("tag", sorted(PE))
+@pytest.mark.parametrize("tag", sorted(PE) + ["protrude"])
 def test_clipping_paired(tag, tmp_path, built):
-    info = dict(prepare("pe101", str(tmp_path), need_ref=False))
-    ref, new = _run(info, tag, PE[tag], tmp_path, adapters=(AD1, AD2))
+    info = dict(prepare("pe76_overlap" if tag == "protrude" else "pe101", str(tmp_path), need_ref=False))
+    ref, new = _run(info, tag, PROTRUDE if tag == "protrude" else PE[tag], tmp_path, adapters=(AD1, AD2))
     assert not compare_outputs(ref, new)
 
 

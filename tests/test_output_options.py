@@ -14,6 +14,9 @@ CASES = {
     "rg1": ["--outSAMattrRGline", "ID:only", "CN:c", "--outSAMattributes", "NH", "HI", "RG", "AS"],
     "unm": ["--outReadsUnmapped", "Fastx", "--outSAMreadID", "Number", "--outFilterScoreMinOverLread", "0.9", "--outFilterMatchNminOverLread", "0.9"],
     "mult": ["--outSAMmultNmax", "1", "--outSAMtlen", "2"],
+    # --outSAMmode NoQS: "*" in mapped records; unmapped records keep their qualities in SAM and lose them in BAM, as in the reference
+    "noqs": ["--outSAMmode", "NoQS", "--outSAMunmapped", "Within"],
+    "noqs_bam": ["--outSAMmode", "NoQS", "--outSAMunmapped", "Within", "--outSAMtype", "BAM", "Unsorted", "SortedByCoordinate"],
     "bam": ["--outSAMtype", "BAM", "Unsorted", "SortedByCoordinate", "--outSAMtlen", "2", "--outSAMattrRGline", "ID:q", "--outSAMunmapped", "Within", "--outSAMmultNmax", "2"],
 }
 
@@ -44,7 +47,7 @@ def test_output_options(name, tag, tmp_path, built):
     ref = refstar.align(info["idx"], info["fastq"], os.path.join(d, "ref_"), threads=1, extra=info["extra"])
     new = run_with_engine(info, os.path.join(d, "new_"), lambda g, p: oracle_lib.Oracle(g, p), batch_reads=450)
     rg = lambda t: [l for l in t.split(b"\n") if l.startswith(b"@RG")]
-    if tag == "bam":
+    if tag in ("bam", "noqs_bam"):
         for f in ("Aligned.out.bam", "Aligned.sortedByCoord.out.bam"):
             (ta, ra, rr), (tb, rb, nr) = bam_parts(ref + f), bam_parts(new + f)
             assert ra == rb and rr == nr, f
