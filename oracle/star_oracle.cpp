@@ -748,7 +748,16 @@ struct Oracle {
     // ------------------------------------------------------------------ ReadAlign_stitchPieces.cpp:12-350
     // returns status bits; fills trAll
     uint32_t stitchPieces(int &trBestW) {
-        uint32_t status = 0;
+        buildWindows();
+        return stitchWindows(trBestW);
+    }
+    // :12-185: windows from the anchors, flanks, every seed locus into its window (what k_window.hip replaces; oracle/window_routines_check.cpp compares it alone)
+    void buildWindows() {
+        createWindows();
+        assignSeeds();
+    }
+    // :12-127: pass A and the flanks
+    void createWindows() {
         std::fill(winBin[0].begin(), winBin[0].end(), 0xFFFF);
         std::fill(winBin[1].begin(), winBin[1].end(), 0xFFFF);
         nW = 0; WC.clear();
@@ -784,6 +793,9 @@ struct Oracle {
         }
         WA.assign(nW, std::vector<WAlign>()); WALrec.assign(nW, 0);
         cnt[C_nWindows] += nW;
+    }
+    // :129-185: every seed locus into the window that owns its bin
+    void assignSeeds() {
         u64 nWpassB = nW;
         for (u64 iP = 0; iP < PC.size(); iP++) {
             u64 aNrep = PC[iP].nrep, aFrag = PC[iP].iFrag, aLength = PC[iP].L, aDir = PC[iP].dir;
@@ -805,6 +817,10 @@ struct Oracle {
             }
         }
         (void)nWpassB;
+    }
+    // :187-350: the windows stitched one by one
+    uint32_t stitchWindows(int &trBestW) {
+        uint32_t status = 0;
         if (tooManyAnchors) status |= STARAMD_ST_TOO_MANY_ANCHORS;   // nW was set to 0 (assignAlignToWindow.cpp:76-80)
         if (windowsLimit) status |= STARAMD_ST_WINDOWS_LIMIT;
         trAll.clear();

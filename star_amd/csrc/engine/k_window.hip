@@ -431,7 +431,7 @@ template <bool BIG> __device__ __forceinline__ void windowsBody(const DevIndex *
         WPROF_MARK(1);
         // ---- pass B: all seeds (:129-185)
         // the converted one-locus seeds look their windows up together (owner map only: the Bloom-filter form keeps them in the loop); window + 1 takes the chromosome's place
-        const bool uniqB = s.ownMap && !s.overflow;
+        const bool uniqB = !s.overflow && s.ownMap;          // (in this order: after an overflow the flank block has not set ownMap for this read)
         if (uniqB && (uInfo & 0x80000000u)) {
             const u32 w = ownLookup(s.bitmap, s.ownMask, (u32)(myA1 >> P.winBinNbits) * 2u + ((uInfo >> 30) & 1u));
             uInfo = (uInfo & 0xC000FFFFu) | ((w == NOWIN ? 0u : w + 1u) << 16);
