@@ -72,14 +72,8 @@ std::string bgzfCompressDevice(const std::vector<BgzfJob> &jobs, int threads) {
         std::vector<uint64_t> outLen(in.size()), at(in.size() + 1, 0);
         if (g_bgzfFn(g_bgzfUser, level, (uint32_t)in.size(), in.data(), len.data(), buf.get(), cap, outLen.data()) != 0) return "EXITING because of fatal ERROR: BGZF compression failed";
         for (size_t i = 0; i < in.size(); i++) at[i + 1] = at[i] + outLen[i];
-        std::atomic<size_t> next(0);
         const char *base = (const char *)buf.get();          // (the helper threads have thread_local buffers of their own)
-        auto put = [&] { for (size_t i; (i = next.fetch_add(1)) < outs.size();) outs[i]->append(base + at[i], outLen[i]); };
-        std::vector<std::thread> th;
-        const size_t W = std::min<size_t>(outs.size(), (size_t)std::max(1, std::min(threads, 8)));
-        for (size_t w = 1; w < W; w++) th.emplace_back(put);
-        put();
-        for (auto &t : th) t.join();
+        overItems((size_t)std::max(1, std::min(threads, 8)), CPU_NONE, outs.size(), [&](size_t i) { outs[i]->append(base + at[i], outLen[i]); });
     }
     return "";
 }

@@ -16,6 +16,8 @@
 #include <string_view>
 #include <algorithm>
 #include <cassert>
+#include <chrono>
+#include <thread>
 #include "../../../include/star_amd.h"
 #include "../../../include/star_amd_index.h"
 
@@ -29,6 +31,29 @@ struct CpuScope {
     int stage; timespec t0;
     explicit CpuScope(int st) : stage(st) { clock_gettime(CLOCK_THREAD_CPUTIME_ID, &t0); }
     ~CpuScope() { timespec t1; clock_gettime(CLOCK_THREAD_CPUTIME_ID, &t1); cpuAdd(stage, (uint64_t)((t1.tv_sec - t0.tv_sec) * 1000000000ll + (t1.tv_nsec - t0.tv_nsec))); }
+};
+
+// ---- the helper threads a stage starts for one piece of work.  onThreads: share(w) runs for every w in [0, W), w = 0 on the calling thread and the others on W - 1
+// threads that live for the call.  overItems: item(i) runs for every i in [0, n), each taken from a shared counter by one of min(W, n) such threads (a thread that is
+// done with an item takes the next one: the call lasts as long as its slowest item, not as its slowest share).  `stage` is the CpuScope of the HELPER threads (the
+// calling thread carries its own, see above); CPU_NONE: the work is not part of a stage that sah_cpu_seconds reports
+enum { CPU_NONE = -1 };
+template <class F> void onThreads(size_t W, int stage, F &&share) {
+    std::vector<std::thread> th;
+    for (size_t w = 1; w < W; w++) th.emplace_back([&share, stage, w] { if (stage == CPU_NONE) { share(w); return; } CpuScope cs(stage); share(w); });
+    share((size_t)0);
+    for (auto &x : th) x.join();
+}
+template <class F> void overItems(size_t W, int stage, size_t n, F &&item) {
+    std::atomic<size_t> next(0);
+    onThreads(std::min(W, n), stage, [&](size_t) { for (size_t i; (i = next.fetch_add(1)) < n;) item(i); });
+}
+// wall-clock time of a scope, added to *acc when the scope ends, in units of 1 / perSecond seconds (1e3: ms); acc == nullptr: not measured
+struct ScopedTimer {
+    typedef std::chrono::steady_clock Clock;
+    double *acc; double perSecond; Clock::time_point t0;
+    explicit ScopedTimer(double *acc, double perSecond = 1.0, Clock::time_point t0 = Clock::now()) : acc(acc), perSecond(perSecond), t0(t0) {}
+    ~ScopedTimer() { if (acc) *acc += perSecond * std::chrono::duration<double>(Clock::now() - t0).count(); }
 };
 
 // ---- genomeDir on disk -> host arrays (Genome::genomeLoad, source/Genome_genomeLoad.cpp:18-467) ----
@@ -154,6 +179,7 @@ struct RunParams {
     int readFilesSAMmates = 0;           // --readFilesType SAM SE | PE: 1 | 2 (0 = Fastx)
     bool samAttrKeepAll = true, samAttrKeepNone = false; std::vector<std::string> samAttrKeep;   // --readFilesSAMattrKeep (BAM output only, Parameters_readFilesInit.cpp:13-31)
     uint32_t peOverlapNbasesMin = 0; double peOverlapMMp = 0.01;   // --peOverlapNbasesMin, --peOverlapMMp
+    bool mergedMates() const { return peOverlapNbasesMin > 0 && dev.readNmates == 2; }   // the overlapping mates of a batch, merged, are mapped as a second batch
     bool outSAMorderKeep = false;        // --outSAMorder PairedKeepInputOrder
     bool outSJnone = false;              // --outSJtype None
     int outQSconversionAdd = 0;          // --outQSconversionAdd (readLoad.cpp:71-82)

@@ -297,12 +297,6 @@ uint64_t FastqReader::fillMapped(int m, uint64_t want, ReadBatch &b) {
     b.mapped[m] = tx;
     const uint64_t wantLines = want * 4;
     static const uint64_t sliceMin = getenv("STARAMD_READ_SLICE_MIN") ? strtoull(getenv("STARAMD_READ_SLICE_MIN"), nullptr, 10) : (8u << 20);
-    auto onThreads = [&](unsigned K, const std::function<void(unsigned)> &fn) {
-        std::vector<std::thread> th;
-        for (unsigned k = 1; k < K; k++) th.emplace_back([&fn, k] { CpuScope cs(CPU_FILL); fn(k); });
-        fn(0);
-        for (auto &x : th) x.join();
-    };
     uint64_t scanned = 0;
     while (nlp.size() < wantLines && scanned < avail) {
         const uint64_t missing = (wantLines - nlp.size() + 3) / 4;
@@ -311,7 +305,7 @@ uint64_t FastqReader::fillMapped(int m, uint64_t want, ReadBatch &b) {
             const unsigned K = std::max(1u, readSlices);
             std::vector<std::vector<uint64_t>> nl(K);
             const uint64_t per = (block + K - 1) / K;
-            onThreads(K, [&](unsigned k) {
+            onThreads(K, CPU_FILL, [&](unsigned k) {
                 const uint64_t lo = std::min(block, k * per), hi = std::min(block, lo + per);
                 nl[k].reserve((size_t)((double)(hi - lo) / bytesPerRecord[m] * 4.2) + 16);
                 scanNewlines(tx, scanned + lo, scanned + hi, nl[k], UINT64_MAX);
@@ -320,7 +314,7 @@ uint64_t FastqReader::fillMapped(int m, uint64_t want, ReadBatch &b) {
             for (unsigned k = 0; k < K; k++) off[k + 1] = off[k] + nl[k].size();
             const size_t total = std::min<size_t>(off[K], wantLines);
             nlp.resize(total);
-            onThreads(K, [&](unsigned k) { if (off[k] < total) memcpy(nlp.data() + off[k], nl[k].data(), (std::min(off[k + 1], total) - off[k]) * sizeof(uint64_t)); });
+            onThreads(K, CPU_FILL, [&](unsigned k) { if (off[k] < total) memcpy(nlp.data() + off[k], nl[k].data(), (std::min(off[k + 1], total) - off[k]) * sizeof(uint64_t)); });
             slicedBlocks++;
         } else scanNewlines(tx, scanned, scanned + block, nlp, wantLines);
         scanned += block;
@@ -333,7 +327,7 @@ uint64_t FastqReader::fillMapped(int m, uint64_t want, ReadBatch &b) {
     {
         const unsigned K = nNl >= (1u << 16) ? std::max(1u, readSlices) : 1u;
         const size_t per = (nNl + K - 1) / K;
-        onThreads(K, [&](unsigned k) {
+        onThreads(K, CPU_FILL, [&](unsigned k) {
             const size_t lo = std::min(nNl, k * per), hi = std::min(nNl, lo + per);
             for (size_t i = lo; i < hi; i++) {
                 const uint64_t s0 = i ? nlp[i - 1] + 1 : 0; uint64_t e0 = nlp[i];
@@ -372,12 +366,6 @@ uint64_t FastqReader::fill(int m, uint64_t want, ReadBatch &b) {
     auto Tf = std::chrono::steady_clock::now(); double msRead = 0, msMerge = 0;
     auto lapf = [&](double &acc) { if (timing) { auto t = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::milli>(t - Tf).count(); Tf = t; } };
     static const uint64_t sliceMin = getenv("STARAMD_READ_SLICE_MIN") ? strtoull(getenv("STARAMD_READ_SLICE_MIN"), nullptr, 10) : (8u << 20);   // (tests lower it)
-    auto onThreads = [&](unsigned K, const std::function<void(unsigned)> &fn) {
-        std::vector<std::thread> th;
-        for (unsigned k = 1; k < K; k++) th.emplace_back([&fn, k] { CpuScope cs(CPU_FILL); fn(k); });
-        fn(0);
-        for (auto &x : th) x.join();
-    };
     for (;;) {
         scanned = scanNewlines(text.data(), scanned, text.size(), nlp, wantLines);
         if (nlp.size() >= wantLines || eof[m]) break;
@@ -398,7 +386,7 @@ uint64_t FastqReader::fill(int m, uint64_t want, ReadBatch &b) {
             std::vector<size_t> gotK(K, 0);
             const size_t per = (block + K - 1) / K;
             lapf(msMerge);
-            onThreads(K, [&](unsigned k) {
+            onThreads(K, CPU_FILL, [&](unsigned k) {
                 const size_t lo = std::min<size_t>(block, k * per), hi = std::min<size_t>(block, lo + per);
                 size_t done = 0;
                 while (lo + done < hi) {
@@ -421,7 +409,7 @@ uint64_t FastqReader::fill(int m, uint64_t want, ReadBatch &b) {
             for (unsigned k = 0; k < Kgood; k++) off[k + 1] = off[k] + nl[k].size();
             const size_t total = std::min<size_t>(off[Kgood], wantLines);
             nlp.resize(total);
-            onThreads(Kgood, [&](unsigned k) { if (off[k] < total) memcpy(nlp.data() + off[k], nl[k].data(), (std::min(off[k + 1], total) - off[k]) * sizeof(uint64_t)); });
+            onThreads(Kgood, CPU_FILL, [&](unsigned k) { if (off[k] < total) memcpy(nlp.data() + off[k], nl[k].data(), (std::min(off[k + 1], total) - off[k]) * sizeof(uint64_t)); });
             scanned = nlp.size() >= wantLines ? nlp.back() + 1 : old + got;
             slicedBlocks++;
         }
@@ -440,7 +428,7 @@ uint64_t FastqReader::fill(int m, uint64_t want, ReadBatch &b) {
         const char *tx = text.data();
         const unsigned K = nNl >= (1u << 16) ? std::max(1u, readSlices) : 1u;
         const size_t per = (nNl + K - 1) / K;
-        onThreads(K, [&](unsigned k) {
+        onThreads(K, CPU_FILL, [&](unsigned k) {
             const size_t lo = std::min(nNl, k * per), hi = std::min(nNl, lo + per);
             for (size_t i = lo; i < hi; i++) {
                 const uint64_t s0 = i ? nlp[i - 1] + 1 : 0; uint64_t e0 = nlp[i];
@@ -522,7 +510,7 @@ bool FastqReader::fillBatch(ReadBatch &b, const RunParams &P, uint64_t maxReads,
     for (;;) {
         if (useMap < 0) useMap = (!fromMemory && samMates_ == 0 && !fasta && command_.empty() && P.outQSconversionAdd == 0 && !P.outSAMreadIDnumber && curMap[0].p && (nMates < 2 || curMap[1].p)) ? 1 : 0;
         if (nMates == 2 && samMates_ == 0 && !fasta) {       // the two mate files are read and scanned for line ends side by side
-            std::thread second([&] { CpuScope cs(CPU_FILL); nLines[1] = fill(1, want, b); });
+            std::thread second([&] { CpuScope cs(CPU_FILL); nLines[1] = fill(1, want, b); });      // (two different calls with a result each, not shares of one: no onThreads)
             nLines[0] = fill(0, want, b);
             second.join();
         } else
@@ -571,11 +559,8 @@ bool FastqReader::convertBatch(ReadBatch &b, const RunParams &P, std::string &er
     std::atomic<uint64_t> firstBad(UINT64_MAX);
     std::vector<std::string> errs(T);
     auto inRanges = [&](const std::function<void(uint64_t, uint64_t, int)> &fn) {
-        if (T == 1) { fn(0, n, 0); return; }
-        std::vector<std::thread> th;
-        uint64_t per = (n + T - 1) / T;
-        for (int t = 0; t < T; t++) th.emplace_back([&, t] { CpuScope cs(CPU_CONVERT); uint64_t lo = std::min<uint64_t>(n, t * per), hi = std::min<uint64_t>(n, lo + per); fn(lo, hi, t); });
-        for (auto &x : th) x.join();
+        const uint64_t per = (n + T - 1) / T;
+        onThreads((size_t)T, CPU_CONVERT, [&](size_t t) { uint64_t lo = std::min<uint64_t>(n, t * per), hi = std::min<uint64_t>(n, lo + per); fn(lo, hi, (int)t); });
     };
     // pass 1: spans, checks, lengths
     inRanges([&](uint64_t lo, uint64_t hi, int t) {
@@ -743,6 +728,7 @@ void MergedBatch::build(const ReadBatch &b, const RunParams &P) {
     };
     if (T == 1) search(0, n);
     else {
+        // (not onThreads: that runs one share on the caller, whose CpuScope -- the convert stage -- would then count work that no stage counts today)
         std::vector<std::thread> th; const uint32_t per = (n + T - 1) / T;
         for (int t = 0; t < T; t++) th.emplace_back(search, std::min(n, (uint32_t)t * per), std::min(n, (uint32_t)(t + 1) * per));
         for (auto &x : th) x.join();

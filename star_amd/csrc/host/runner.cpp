@@ -3,6 +3,11 @@
 // The engine (HIP library behind include/star_amd.h) is NOT linked here: callers pass result buffers in,
 // so the same post-map code is exercised with results produced by the HIP engine (product) or,
 // in tests only, by the CPU oracle.
+//
+// In this file: BatchSet (a batch with its merged mates and WASP reads: the main batch and every slot), EmitRange (everything one range of a batch
+// produces), SamWriter (the writer thread of Aligned.out.sam / .bam and its two sets of ranges), Runner (the run: init, the batch operations on a
+// BatchSet, emitBatch = planEmit / drawRandomOrder / formatRange / compressOnDevice / foldRanges, the phase changes, finish), then the C interface,
+// whose batch operations forward to Runner with the set and the error string of the calling stage.
 #include "host.h"
 #include <unistd.h>
 #include <fcntl.h>
@@ -25,17 +30,129 @@
 
 namespace staramd {
 
+// one batch with what is mapped beside it: the main batch of the one-batch-at-a-time interface (sah_next_batch ...) and every slot of the pipelined one
+// (sah_fill_slot ...) are such a set, and each batch operation has one body that takes the set
+struct BatchSet {
+    ReadBatch batch;
+    MergedBatch merged;     // --peOverlapNbasesMin: the merged mates of `batch`, mapped as a second batch
+    WaspBatch wasp;         // --waspOutputMode SAMtag: the allele-swapped reads of `batch`, mapped as one more batch
+};
+
+// Everything one range of reads of a batch produces (Runner::emitBatch).  A worker thread appends to the members of ITS range for the length of the range, and a
+// std::string / std::vector rewrites its size word on every append: two ranges never share a cache line (as neighbouring elements of per-output vectors they did,
+// measured 4x per record with 8 threads).  The ranges live in the writer's two sets and keep their capacity between batches: a fresh buffer grows by reallocation
+// up to a few hundred KB per range and batch, which glibc serves with mmap / munmap -- page faults on every batch.
+struct alignas(64) EmitRange {
+    std::string sam;                            // what goes to Aligned.out.sam / .bam: SAM text or BGZF blocks
+    std::string raw;                            // BAM: the records, uncompressed
+    OutSJ sj; Stats st;
+    OutSJ sj1; std::vector<uint32_t> held;      // 1st stage of BySJout: junctions of every read, reads held for the 2nd stage
+    GeneCounts gc;                              // --quantMode GeneCounts
+    std::vector<BamKey> keys;                   // --outSAMtype BAM SortedByCoordinate
+    std::string quantRaw, quantZ; std::vector<QuantPatch> quantPatches;     // --quantMode TranscriptomeSAM: records, their BGZF blocks, where the primary flag goes
+    std::string only; bool cut = false;         // KeepPairs with both BAM files: `raw` without the records of the sorted file (what the unsorted one gets)
+    std::string chim, chimSam;                  // Chimeric.out.junction lines, Chimeric.out.sam records
+    std::string unmapped[2];                    // --outReadsUnmapped Fastx, per mate
+    std::string err; double ms = 0;             // error text of the range; time on its worker (STARAMD_HOST_TIMING)
+    void reset(bool geneCounts, size_t nGenes) {
+        sam.clear(); raw.clear(); sj.data.clear(); st = Stats(); sj1.data.clear(); held.clear(); keys.clear();
+        if (geneCounts) gc = GeneCounts(nGenes);
+        quantRaw.clear(); quantZ.clear(); quantPatches.clear(); only.clear(); cut = false; chim.clear(); chimSam.clear(); unmapped[0].clear(); unmapped[1].clear();
+        err.clear(); ms = 0;
+    }
+};
+
+// ---- Aligned.out.sam / Aligned.out.bam go to the file on a thread of their own: formatting of batch k+1 overlaps the write of batch k.  Two sets of ranges
+// alternate.  The emit side takes a free set, fills ranges[0 .. used) and hands it over; the writer puts out the `sam` of every range, in range order, and frees the set.
+struct SamWriter {
+    struct Set { std::vector<EmitRange> ranges; uint32_t used = 0; };
+    uint64_t mappedWrites = 0;               // batches whose text went out through a mapping of the output file (sah_fast_path_counts)
+    double seconds = 0;                      // busy time, whole run
+    void start(FILE *out, int runThreadN) {
+        samOut = out;
+        wantMmap = getenv("STARAMD_WRITER_MMAP") ? atoi(getenv("STARAMD_WRITER_MMAP")) : 1;
+        // (follows --runThreadN like every helper count; 8 of 16: the writer is level with the kernels now, 4 copy threads lost 2 % to 8 on one box -- profiles/r06_e2e_session37_*)
+        wantW = getenv("STARAMD_WRITER_THREADS") ? (uint32_t)std::max(1, atoi(getenv("STARAMD_WRITER_THREADS"))) : (uint32_t)std::max(1, std::min(8, runThreadN / 2));
+        pwriteW = getenv("STARAMD_WRITER_PWRITE_THREADS") ? (uint32_t)std::max(1, atoi(getenv("STARAMD_WRITER_PWRITE_THREADS"))) : 2u;      // (positional writes: 1 = one stream, no contention for the inode lock)
+        freeSets = {0, 1};
+        thread = std::thread([this] { loop(); });
+    }
+    Set &takeFree() { std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return !freeSets.empty(); }); const int k = freeSets.front(); freeSets.pop_front(); return sets[k]; }
+    void handOver(Set &s) { { std::lock_guard<std::mutex> l(m); fullSets.push_back((int)(&s - sets)); } cv.notify_all(); }
+    void stop() {           // after the sets that were handed over are written
+        if (!thread.joinable()) return;
+        { std::lock_guard<std::mutex> l(m); stopping = true; }
+        cv.notify_all();
+        thread.join();
+    }
+    bool failed() const { return bad.load(); }
+    void resumeStream() { if (fd >= 0) { fflush(samOut); fseeko(samOut, (off_t)pos, SEEK_SET); } }      // the batches went out through positional writes: the stream goes on behind them
+    ~SamWriter() { stop(); }
+private:
+    Set sets[2];
+    std::mutex m; std::condition_variable cv;
+    std::deque<int> freeSets, fullSets; bool stopping = false; std::atomic<bool> bad{false};
+    std::thread thread;
+    FILE *samOut = nullptr;
+    int fd = -1; uint64_t pos = 0;           // positional writes of the SAM / unsorted BAM text (regular file)
+    int seekable = -1;                       // -1 not looked at yet, 0 pipe / FIFO / character device (sequential fwrite), 1 regular file
+    int wantMmap = 1; uint32_t wantW = 1, pwriteW = 2;      // STARAMD_WRITER_MMAP, _WRITER_THREADS, _WRITER_PWRITE_THREADS
+    void loop() {
+        for (;;) {
+            int k;
+            { std::unique_lock<std::mutex> l(m); cv.wait(l, [&] { return !fullSets.empty() || stopping; }); if (fullSets.empty()) return; k = fullSets.front(); fullSets.pop_front(); }
+            write(sets[k]);
+            { std::lock_guard<std::mutex> l(m); freeSets.push_back(k); }
+            cv.notify_all();
+        }
+    }
+    void write(Set &o) {
+        CpuScope cpuScope(CPU_WRITE);
+        ScopedTimer addTime(&seconds);
+        if (seekable < 0 && samOut) {            // a named pipe (mkfifo Aligned.out.sam | samtools ...) or a device has no offsets: pwrite fails with ESPIPE there
+            struct stat st; seekable = (samOut != stdout && fstat(fileno(samOut), &st) == 0 && S_ISREG(st.st_mode) && ftello(samOut) >= 0) ? 1 : 0;
+        }
+        if (!(samOut && seekable == 1 && (o.used > 1 || fd >= 0 || wantMmap >= 2))) {
+            for (uint32_t t = 0; t < o.used; t++) {
+                const std::string &s = o.ranges[t].sam;
+                if (!s.empty() && samOut && fwrite(s.data(), 1, s.size(), samOut) != s.size()) bad = true;
+            }
+            return;
+        }
+        // a regular file: the ranges' text buffers go out side by side, each at its own offset (one fwrite stream tops out near
+        // 2 GB/s on tmpfs, the SAM text of one GPU runs at about that)
+        if (fd < 0) { fflush(samOut); fd = fileno(samOut); pos = (uint64_t)ftello(samOut); }
+        std::vector<uint64_t> at(o.used + 1, pos);
+        for (uint32_t t = 0; t < o.used; t++) at[t + 1] = at[t] + o.ranges[t].sam.size();
+        // write() / pwrite() into ONE file are serialised by the inode lock (tmpfs: 2.9 GB/s from two threads on a box whose tmpfs takes 5.8 / 11.7 / 18.5 GB/s from
+        // 1 / 2 / 4 streams into separate files: the SAM writer at 230 MB per batch was the slowest stage of the pipeline there, 80 ms against 52 ms of kernels).  So the
+        // file is grown to the batch's end and the new part mapped: the threads copy their ranges into the mapping and take their page faults side by side.
+        const uint64_t total = at[o.used] - pos;
+        char *map = nullptr; uint64_t mapOff = 0, mapLen = 0;
+        // the blocks are reserved before they are written to (posix_fallocate also sets the new size): a full file system is an error return here, not a SIGBUS in a copy
+        if (wantMmap && total > 0 && (wantMmap >= 2 || total >= (1u << 20)) && posix_fallocate(fd, (off_t)pos, (off_t)total) == 0) {      // (2: whatever the size -- tests)
+            static const uint64_t page = (uint64_t)std::max<long>(sysconf(_SC_PAGESIZE), 4096); mapOff = pos & ~(page - 1); mapLen = at[o.used] - mapOff;
+            void *mm = mmap(nullptr, (size_t)mapLen, PROT_READ | PROT_WRITE, MAP_SHARED, fd, (off_t)mapOff);
+            if (mm != MAP_FAILED) { map = (char *)mm; mappedWrites++; }
+        }
+        overItems(map ? wantW : pwriteW, CPU_WRITE, o.used, [&](size_t t) {
+            const std::string &s = o.ranges[t].sam;
+            const char *p = s.data(); uint64_t left = s.size(), off = at[t];
+            if (map) { if (left) memcpy(map + (off - mapOff), p, left); return; }
+            while (left && !bad) { ssize_t w = pwrite(fd, p, left, (off_t)off); if (w <= 0) { bad = true; return; } p += w; left -= (uint64_t)w; off += (uint64_t)w; }
+        });
+        if (map) munmap(map, (size_t)mapLen);
+        pos = at[o.used];
+    }
+};
+
 struct Runner {
     RunParams P;
     GenomeIndex gi;
     FastqReader reader;
-    ReadBatch batch;
-    staramd_batch batchView;
     static const int NSLOT = 24;        // batch slots of the pipelined CLI (3 + 2 per GPU are in use: cli_run.cpp)
-    ReadBatch slots[NSLOT];             // pipelined CLI: parse / map / post-map work on different slots
+    BatchSet mainSet, slots[NSLOT];     // pipelined CLI: parse / map / post-map work on different slots
     Variation variation;                      // --varVCFfile
-    WaspBatch waspMain, waspSlots[NSLOT];         // --waspOutputMode SAMtag: the allele-swapped reads of batch / slots[k], mapped as one more batch
-    MergedBatch mergedMain, mergedSlots[NSLOT];   // --peOverlapNbasesMin: the merged mates of batch / slots[k], mapped as a second batch
     std::unique_ptr<PostMap> post;
     OutSJ sj;
     Stats stats;
@@ -211,275 +328,202 @@ struct Runner {
                 fclose(lp);
             }
         }
-        startWriter();
+        writer.start(samOut, P.runThreadN);
         time(&stats.timeStartMap);
         return true;
     }
-    int nextBatch(uint64_t maxReads) {
+    // ---- the batch operations of the C interface, one body each.  `s` is the main set or a slot; `sink` is the error string of the stage that calls (see above)
+    void report(std::string &sink, const std::string &msg) { std::lock_guard<std::mutex> l(errM); sink = msg; }
+    int converted(BatchSet &s, staramd_batch *out) { if (out) *out = s.batch.view(); if (P.mergedMates()) s.merged.build(s.batch, P); return (int)s.batch.n; }
+    int parseBatch(BatchSet &s, uint64_t maxReads, staramd_batch *out, std::string &sink) {
         std::string err;
-        bool ok = reader.nextBatch(batch, P, maxReads, err);
-        if (!err.empty()) { error = err; return -1; }
-        if (!ok) return 0;
-        batchView = batch.view();
-        if (P.peOverlapNbasesMin > 0 && P.dev.readNmates == 2) mergedMain.build(batch, P);
-        return (int)batch.n;
+        const bool ok = reader.nextBatch(s.batch, P, maxReads, err);
+        if (!err.empty()) { report(sink, err); return -1; }
+        return ok ? converted(s, out) : 0;
     }
-    // ---- SAM text goes to the file on its own thread: formatting of batch k+1 overlaps the write of batch k.  Two sets of
-    // per-thread text buffers alternate and keep their capacity (no fresh pages per batch).
-    struct OutSet { std::vector<std::string> sams, raws; uint32_t used = 0; };
-    std::vector<OutSJ> sjScratch;            // emitBatch: junction records per thread (one batch at a time)
-    OutSet outSets[2];
-    std::mutex wm; std::condition_variable wcv;
-    std::deque<int> freeSets, fullSets; bool writerStop = false, writerFailed = false;
-    std::thread writerThread;
-    int samFd = -1; uint64_t samPos = 0;     // positional writes of the SAM / unsorted BAM text (regular file)
-    int samSeekable = -1;                    // -1 not looked at yet, 0 pipe / FIFO / character device (sequential fwrite), 1 regular file
-    uint64_t nMappedWrites = 0;              // batches whose text went out through a mapping of the output file (sah_fast_path_counts)
-    double tWriter = 0, tEmitWaitSet = 0, tEmitFormat = 0, tEmitTail = 0;      // seconds, whole run (STARAMD_HOST_TIMING prints them at the end)
-    void writerLoop() {
-        for (;;) {
-            int k;
-            { std::unique_lock<std::mutex> l(wm); wcv.wait(l, [&] { return !fullSets.empty() || writerStop; }); if (fullSets.empty()) return; k = fullSets.front(); fullSets.pop_front(); }
-            OutSet &o = outSets[k];
-            CpuScope cpuScope(CPU_WRITE);
-            const auto tw0 = std::chrono::steady_clock::now();
-            struct AddTime { double &acc; std::chrono::steady_clock::time_point t0; ~AddTime() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } addTime{tWriter, tw0};
-            if (samSeekable < 0 && samOut) {            // a named pipe (mkfifo Aligned.out.sam | samtools ...) or a device has no offsets: pwrite fails with ESPIPE there
-                struct stat st; samSeekable = (samOut != stdout && fstat(fileno(samOut), &st) == 0 && S_ISREG(st.st_mode) && ftello(samOut) >= 0) ? 1 : 0;
-            }
-            static const int wantMmap = getenv("STARAMD_WRITER_MMAP") ? atoi(getenv("STARAMD_WRITER_MMAP")) : 1;
-            if (samOut && samSeekable == 1 && (o.used > 1 || samFd >= 0 || wantMmap >= 2)) {
-                // a regular file: the per-thread text buffers go out side by side, each at its own offset (one fwrite stream tops out near
-                // 2 GB/s on tmpfs, the SAM text of one GPU runs at about that)
-                if (samFd < 0) { fflush(samOut); samFd = fileno(samOut); samPos = (uint64_t)ftello(samOut); }
-                std::vector<uint64_t> at(o.used + 1, samPos);
-                for (uint32_t t = 0; t < o.used; t++) at[t + 1] = at[t] + o.sams[t].size();
-                // write() / pwrite() into ONE file are serialised by the inode lock (tmpfs: 2.9 GB/s from two threads on a box whose tmpfs takes 5.8 / 11.7 / 18.5 GB/s from
-                // 1 / 2 / 4 streams into separate files: the SAM writer at 230 MB per batch was the slowest stage of the pipeline there, 80 ms against 52 ms of kernels).  So the
-                // file is grown to the batch's end and the new part mapped: the threads copy their ranges into the mapping and take their page faults side by side.
-                const uint32_t wantW = getenv("STARAMD_WRITER_THREADS") ? (uint32_t)std::max(1, atoi(getenv("STARAMD_WRITER_THREADS"))) : (uint32_t)std::max(1, std::min(8, P.runThreadN / 2));      // (follows --runThreadN like every helper count; 8 of 16: the writer is level with the kernels now, 4 copy threads lost 2 % to 8 on one box -- profiles/r06_e2e_session37_*)
-                const uint64_t total = at[o.used] - samPos;
-                char *map = nullptr; uint64_t mapOff = 0, mapLen = 0;
-                // the blocks are reserved before they are written to (posix_fallocate also sets the new size): a full file system is an error return here, not a SIGBUS in a copy
-                if (wantMmap && total > 0 && (wantMmap >= 2 || total >= (1u << 20)) && posix_fallocate(samFd, (off_t)samPos, (off_t)total) == 0) {      // (2: whatever the size -- tests)
-                    static const uint64_t page = (uint64_t)std::max<long>(sysconf(_SC_PAGESIZE), 4096); mapOff = samPos & ~(page - 1); mapLen = at[o.used] - mapOff;
-                    void *m = mmap(nullptr, (size_t)mapLen, PROT_READ | PROT_WRITE, MAP_SHARED, samFd, (off_t)mapOff);
-                    if (m != MAP_FAILED) { map = (char *)m; nMappedWrites++; }
-                }
-                static const uint32_t pwriteW = getenv("STARAMD_WRITER_PWRITE_THREADS") ? (uint32_t)std::max(1, atoi(getenv("STARAMD_WRITER_PWRITE_THREADS"))) : 2u;      // (positional writes: 1 = one stream, no contention for the inode lock)
-                const uint32_t W = std::min<uint32_t>(map ? wantW : pwriteW, o.used);
-                std::atomic<uint32_t> next(0); std::atomic<bool> bad(false);
-                auto put = [&] {
-                    for (;;) {
-                        uint32_t t = next.fetch_add(1);
-                        if (t >= o.used) break;
-                        const char *p = o.sams[t].data(); uint64_t left = o.sams[t].size(), off = at[t];
-                        if (map) { if (left) memcpy(map + (off - mapOff), p, left); continue; }
-                        while (left) { ssize_t w = pwrite(samFd, p, left, (off_t)off); if (w <= 0) { bad = true; return; } p += w; left -= (uint64_t)w; off += (uint64_t)w; }
-                    }
-                };
-                std::vector<std::thread> th;
-                for (uint32_t i = 1; i < W; i++) th.emplace_back([&] { CpuScope cs(CPU_WRITE); put(); });
-                put();
-                for (auto &x : th) x.join();
-                if (map) munmap(map, (size_t)mapLen);
-                samPos = at[o.used];
-                if (bad) writerFailed = true;
-            } else
-            for (uint32_t t = 0; t < o.used; t++)
-                if (!o.sams[t].empty() && samOut && fwrite(o.sams[t].data(), 1, o.sams[t].size(), samOut) != o.sams[t].size()) writerFailed = true;
-            { std::lock_guard<std::mutex> l(wm); freeSets.push_back(k); }
-            wcv.notify_all();
-        }
+    int mergedBatch(BatchSet &s, staramd_batch *out) { if (!P.mergedMates() || s.merged.reads.n == 0) return 0; if (out) *out = s.merged.reads.view(); return (int)s.merged.reads.n; }
+    int waspBatch(BatchSet &s, const staramd_results *res, staramd_batch *out) {
+        if (!P.wasp || pass1) return 0;
+        s.wasp.build(P, gi, variation, s.batch, *res);
+        if (out) *out = s.wasp.reads.view();
+        return (int)s.wasp.reads.n;
     }
-    void startWriter() { freeSets = {0, 1}; writerThread = std::thread([this] { writerLoop(); }); }
-    void stopWriter() {
-        if (!writerThread.joinable()) return;
-        { std::lock_guard<std::mutex> l(wm); writerStop = true; }
-        wcv.notify_all();
-        writerThread.join();
+    int waspResults(BatchSet &s, const staramd_results *res, const staramd_results *resWasp, std::string &sink) {
+        if (!P.wasp || pass1 || s.wasp.reads.n == 0) return 0;
+        if (!resWasp) { report(sink, "EXITING because of FATAL ERROR: --waspOutputMode: results of the re-mapped reads are missing"); return -1; }
+        s.wasp.finish(P, s.batch, *res, *resWasp);
+        return 0;
     }
-    // post-map of one batch on --runThreadN host threads: contiguous read ranges, per-thread SAM buffer / junctions / Stats
-    // (what the reference keeps per ReadAlignChunk), SAM text written in read order
-    bool emitBatch(const ReadBatch &bt, const staramd_results *r, const MergedBatch *mg = nullptr, const staramd_results *mgRes = nullptr, const WaspBatch *wasp = nullptr) {
+    bool emitSet(BatchSet &s, const staramd_results *res, const staramd_results *resMerged, bool withMerged = true) {
+        return emitBatch(s.batch, res, withMerged && P.mergedMates() ? &s.merged : nullptr, resMerged, P.wasp ? &s.wasp : nullptr);
+    }
+
+    // ---- post-map of one batch on --runThreadN host threads: contiguous read ranges, each with an EmitRange of its own (what the reference keeps per
+    // ReadAlignChunk), SAM text written in read order.
+    // Which outputs the ranges of a batch produce: decided once per batch, read by the range workers, the counting pass and the fold
+    struct EmitOutputs {
+        bool bamOut;        // BAM records instead of SAM text: a range's records are compressed on its thread, block by block (bgzf.cpp) ...
+        bool devBam;        // ... or, --gpuBAMcompression Device, left uncompressed: one hook call per level compresses them after the join
+        bool coordKeys;     // --outSAMtype BAM SortedByCoordinate: a sort key per record
+        bool stage1;        // 1st stage of --outFilterType BySJout
+        bool geneCounts;    // --quantMode GeneCounts (twoPassRunPass1.cpp:24-29: no quantification in the 1st pass)
+        bool trSAM;         // --quantMode TranscriptomeSAM (twoPassRunPass1.cpp:24-29)
+        bool chim, chimSam; // --chimSegmentMin > 0 (twoPassRunPass1.cpp:24: no chimeric detection in the 1st pass); Chimeric.out.sam
+        bool unmapped;      // --outReadsUnmapped Fastx
+        bool randomOrder;   // --outMultimapperOrder Random
+        bool timing;        // STARAMD_HOST_TIMING
+    };
+    struct EmitPlan {
+        const ReadBatch *bt; const staramd_results *r;
+        const MergedBatch *mg; const staramd_results *mgRes;    // --peOverlapNbasesMin: merged mates and their alignments (null: none in this batch)
+        const std::vector<int8_t> *waspType;                    // vW per read (null: off)
+        EmitOutputs on;
+        uint32_t Wk, T, per;                                    // worker threads, ranges, reads per range
+        EmitRange *ranges;                                      // T of them, in the writer's set
+        int waspEndOfBatch;
+        uint32_t lo(uint32_t t) const { return std::min(bt->n, t * per); }
+        uint32_t hi(uint32_t t) const { return std::min(bt->n, lo(t) + per); }
+    };
+    SamWriter writer;
+    double tEmitWaitSet = 0, tEmitFormat = 0, tEmitTail = 0;      // seconds, whole run (STARAMD_HOST_TIMING prints them at the end)
+
+    // step 1: what the batch brings, which outputs are on, how it is cut into ranges
+    bool planEmit(EmitPlan &pl, const ReadBatch &bt, const staramd_results *r, const MergedBatch *mg, const staramd_results *mgRes, const WaspBatch *wasp) {
         if (P.wasp && !pass1 && !wasp) { error = "EXITING because of FATAL ERROR: --waspOutputMode: the allele-swapped reads of the batch were not mapped (sah_wasp_batch / sah_wasp_results)"; return false; }
-        const std::vector<int8_t> *waspType = (wasp && !pass1) ? &wasp->type : nullptr;
         if (mg && (mg->reads.n == 0 || !mgRes)) { if (mg->reads.n > 0) { error = "EXITING because of FATAL ERROR: --peOverlapNbasesMin: the merged mates of the batch were not mapped (sah_merged_batch / sah_emit_merged)"; return false; } mg = nullptr; }
-        // --gpuBAMcompression Device: the ranges leave their BAM records uncompressed, one hook call per level compresses them after the join
-        const bool devBam = P.gpuBAMdevice && ((((P.outBAMunsorted || P.outBAMcoord) && !post->samOff)) || (P.quantTrSAM && quantOut && !pass1));
-        if (devBam && !bgzfDeviceInstalled()) { error = BGZF_DEVICE_MISSING; return false; }
-        // T contiguous read ranges, each with buffers of its own, formatted by Wk worker threads that take the next range when they are done with one: with as many
+        pl.bt = &bt; pl.r = r; pl.mg = mg; pl.mgRes = mgRes;
+        pl.waspType = (wasp && !pass1) ? &wasp->type : nullptr;
+        static const bool hostTiming = getenv("STARAMD_HOST_TIMING") != nullptr;
+        EmitOutputs &on = pl.on;
+        on.bamOut = (P.outBAMunsorted || P.outBAMcoord) && !post->samOff;
+        on.coordKeys = on.bamOut && P.outBAMcoord;
+        on.stage1 = bySJoutStage == 1;
+        on.geneCounts = P.quantGeneCounts && !pass1;
+        on.trSAM = P.quantTrSAM && quantOut && !pass1;
+        on.devBam = P.gpuBAMdevice && (on.bamOut || on.trSAM);
+        on.chim = P.chim.segmentMin > 0 && !pass1;
+        on.chimSam = on.chim && chimSamOut;
+        on.unmapped = P.outReadsUnmappedFastx && !pass1;
+        on.randomOrder = P.outMultimapperRandom;
+        on.timing = hostTiming;
+        if (on.devBam && !bgzfDeviceInstalled()) { error = BGZF_DEVICE_MISSING; return false; }
+        // T contiguous read ranges, formatted by Wk worker threads that take the next range when they are done with one: with as many
         // ranges as threads the section lasts as long as its slowest thread, and on a shared host (the GPU boxes: 16 CPUs of a 256-thread machine) one descheduled
         // thread held the batch for several times the mean (per-thread busy 2.5 - 5.6 ms in a 24 ms section).  Four ranges per thread; gene counting keeps one
         // (a count table per range)
-        const uint32_t Wk = (uint32_t)std::max(1, std::min(P.runThreadN, 256));
-        uint32_t T = (P.quantGeneCounts || P.quantTrSAM) ? Wk : std::min<uint32_t>(4 * Wk, 256);
-        T = std::max<uint32_t>(1, std::min<uint32_t>(T, bt.n / 256));       // at least 256 reads per range
-        int k;
-        auto te0 = std::chrono::steady_clock::now();
-        { std::unique_lock<std::mutex> l(wm); wcv.wait(l, [&] { return !freeSets.empty(); }); k = freeSets.front(); freeSets.pop_front(); }
-        auto te1 = std::chrono::steady_clock::now(); tEmitWaitSet += std::chrono::duration<double>(te1 - te0).count();
-        OutSet &o = outSets[k];
-        if (o.sams.size() < T) { o.sams.resize(T); o.raws.resize(T); }
-        o.used = T;
-        std::vector<std::string> errs(T); std::vector<Stats> sts(T);
-        // per-thread junction records of the batch: the vectors are kept between batches (a fresh vector grows by reallocation up to a few hundred KB per thread and
-        // batch, which glibc serves with mmap / munmap: page faults on every batch)
-        std::vector<OutSJ> &sjs = sjScratch;
-        if (sjs.size() < T) sjs.resize(T);
-        for (uint32_t t = 0; t < T; t++) sjs[t].data.clear();
-        const bool stage1 = bySJoutStage == 1;
-        std::vector<OutSJ> sj1s(stage1 ? T : 0); std::vector<std::vector<uint32_t> > helds(stage1 ? T : 0);
-        const bool quant = P.quantGeneCounts && !pass1;             // twoPassRunPass1.cpp:24-29: no quantification in the 1st pass
-        std::vector<GeneCounts> gcs(quant ? T : 0, GeneCounts(quant ? genes.geID.size() : 0));
-        std::vector<std::vector<BamKey> > keyss(P.outBAMcoord ? T : 0);
-        const bool trSAM = P.quantTrSAM && quantOut && !pass1;       // twoPassRunPass1.cpp:24-29
-        std::vector<std::string> qraws(trSAM ? T : 0); std::vector<std::vector<QuantPatch> > qpatches(trSAM ? T : 0);
-        std::vector<std::string> onlys(devBam ? T : 0), qzs(devBam && trSAM ? T : 0); std::vector<char> cuts(devBam ? T : 0, 0);
-        const bool chimOn = P.chim.segmentMin > 0 && !pass1;        // twoPassRunPass1.cpp:24: no chimeric detection in the 1st pass
-        std::vector<std::string> chims(chimOn ? T : 0), chimSams(chimOn && chimSamOut ? T : 0);
-        const bool unm = P.outReadsUnmappedFastx && !pass1;
-        std::vector<std::array<std::string, 2> > unms(unm ? T : 0);
-        const bool randomOrder = P.outMultimapperRandom;
-        uint32_t per = (bt.n + T - 1) / T;
-        if (randomOrder) {
-            // with TranscriptomeSAM the shuffles of a read and its draw of the primary transcriptomic alignment alternate in one random stream: the
-            // number of transcriptomic alignments of every read is needed first (it does not depend on the order), so the quantification runs
-            // once into throw-away buffers, then all draws of the batch are made in read order, then the batch is formatted for real
-            std::vector<uint32_t> nAlignT;
-            if (trSAM) {
-                nAlignT.assign(bt.n, 0);
-                auto count = [&](uint32_t t) {
-                    uint32_t lo = std::min(bt.n, t * per), hi = std::min(bt.n, lo + per);
-                    std::string sam0, q0; OutSJ sj0, sj10; Stats st0; std::vector<uint32_t> held0; std::vector<QuantPatch> qp0;
-                    const bool samOff0 = post->samOff;
-                    (void)samOff0;
-                    std::string chim0;      // reads whose chimera goes into the BAM are not quantified: the detection has to run here too
-                    PostMap::RangeOut ro; ro.sam = &sam0; ro.sj = &sj0; ro.st = &st0; if (stage1) { ro.sj1 = &sj10; ro.held = &held0; }
-                    if (chimOn) ro.chimJunction = &chim0;
-                    ro.quantBam = &q0; ro.quantPatches = &qp0;
-                    PostMap::RangeIn ri; ri.dry = true; ri.merged = mg; ri.mergedRes = mgRes;
-                    errs[t] = post->processRange(bt, *r, lo, hi, ro, ri);
-                    for (const QuantPatch &p : qp0) nAlignT[p.ir] = p.nAlignT + 1;
-                };
-                std::atomic<uint32_t> nextC(0);
-                auto countLoop = [&] { for (;;) { const uint32_t t = nextC.fetch_add(1); if (t >= T) break; count(t); } };
-                std::vector<std::thread> th;
-                for (uint32_t w = 1; w < std::min(Wk, T); w++) th.emplace_back([&] { CpuScope cs(CPU_EMIT); countLoop(); });
-                countLoop();
-                for (auto &x : th) x.join();
-            }
-            post->drawMultOrder(bt, *r, [&] { return rngUniformReal0to1(rngMultOrder); }, multOrder, trSAM ? &nAlignT : nullptr, mg, mgRes);
+        pl.Wk = (uint32_t)std::max(1, std::min(P.runThreadN, 256));
+        pl.T = (P.quantGeneCounts || P.quantTrSAM) ? pl.Wk : std::min<uint32_t>(4 * pl.Wk, 256);
+        pl.T = std::max<uint32_t>(1, std::min<uint32_t>(pl.T, bt.n / 256));       // at least 256 reads per range
+        pl.per = (bt.n + pl.T - 1) / pl.T;
+        return true;
+    }
+    // where processRange puts what range `e` produces and what it reads besides the batch: the one statement of it, for the counting pass (dry) and the real one
+    void wireRange(const EmitPlan &pl, EmitRange &e, bool dry, PostMap::RangeOut &ro, PostMap::RangeIn &ri) {
+        const EmitOutputs &on = pl.on;
+        ro.sam = (on.bamOut && !dry) ? &e.raw : &e.sam; ro.sj = &e.sj; ro.st = &e.st;
+        if (on.stage1) { ro.sj1 = &e.sj1; ro.held = &e.held; }
+        if (on.chim) ro.chimJunction = &e.chim;      // (reads whose chimera goes into the BAM are not quantified: the detection has to run in the counting pass too)
+        if (on.trSAM) { ro.quantBam = &e.quantRaw; ro.quantPatches = &e.quantPatches; }
+        ri.dry = dry; ri.merged = pl.mg; ri.mergedRes = pl.mgRes;
+        if (dry) return;                             // the counting pass asks for what decides the number of transcriptomic alignments of a read, nothing else
+        if (on.geneCounts) ro.gc = &e.gc;
+        if (on.coordKeys) ro.bamKeys = &e.keys;
+        if (on.unmapped) ro.unmappedFastx = e.unmapped;
+        if (on.chimSam) ro.chimSam = &e.chimSam;
+        ri.order = on.randomOrder ? &multOrder : nullptr; ri.waspType = pl.waspType;
+    }
+    // step 2 (--outMultimapperOrder Random): all draws of the batch, in read order, from the run's one random stream
+    void drawRandomOrder(const EmitPlan &pl) {
+        // with TranscriptomeSAM the shuffles of a read and its draw of the primary transcriptomic alignment alternate in one random stream: the
+        // number of transcriptomic alignments of every read is needed first (it does not depend on the order), so the quantification runs
+        // once into throw-away ranges, then all draws of the batch are made in read order, then the batch is formatted for real
+        std::vector<uint32_t> nAlignT;
+        if (pl.on.trSAM) {
+            nAlignT.assign(pl.bt->n, 0);
+            overItems(pl.Wk, CPU_EMIT, pl.T, [&](size_t t) {
+                EmitRange e0; PostMap::RangeOut ro; PostMap::RangeIn ri;
+                wireRange(pl, e0, true, ro, ri);
+                post->processRange(*pl.bt, *pl.r, pl.lo((uint32_t)t), pl.hi((uint32_t)t), ro, ri);      // (an error comes back from the real pass)
+                for (const QuantPatch &p : e0.quantPatches) nAlignT[p.ir] = p.nAlignT + 1;
+            });
         }
-        static const bool hostTiming = getenv("STARAMD_HOST_TIMING") != nullptr;
-        std::vector<double> tThread(hostTiming ? T : 0);
-        const double msBefore = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te1).count();
-        int waspEndOfBatch = post->waspCarry;
-        auto work = [&](uint32_t t) {
-            struct Tm { std::vector<double> &v; uint32_t t; std::chrono::steady_clock::time_point t0; ~Tm() { if (!v.empty()) v[t] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } } tm{tThread, t, std::chrono::steady_clock::now()};
-            uint32_t lo = std::min(bt.n, t * per), hi = std::min(bt.n, lo + per);
-            // the thread appends to objects of its own for the length of the range: neighbouring elements of the per-thread vectors share
-            // cache lines, and a std::string / std::vector rewrites its size word on every append (measured: 4x per record with 8 threads)
-            std::string samL, rawL; OutSJ sjL; Stats stL;
-            samL.swap(o.sams[t]); rawL.swap(o.raws[t]); sjL.data.swap(sjs[t].data);
-            struct Back { std::string &a, &al, &b, &bl; OutSJ &s, &sl; Stats &st, &stl; ~Back() { a.swap(al); b.swap(bl); s.data.swap(sl.data); st = stl; } } back{o.sams[t], samL, o.raws[t], rawL, sjs[t], sjL, sts[t], stL};
-            samL.clear();
-            const bool bamOut = (P.outBAMunsorted || P.outBAMcoord) && !post->samOff;   // BAM: this thread's records are compressed here, block by block (bgzf.cpp)
-            std::string &raw = rawL;
-            if (bamOut) raw.clear();
-            PostMap::RangeOut ro;
-            ro.sam = bamOut ? &raw : &samL; ro.sj = &sjL; ro.st = &stL;
-            if (stage1) { ro.sj1 = &sj1s[t]; ro.held = &helds[t]; }
-            if (quant) ro.gc = &gcs[t];
-            if (bamOut && P.outBAMcoord) ro.bamKeys = &keyss[t];
-            if (unm) ro.unmappedFastx = unms[t].data();
-            if (chimOn) ro.chimJunction = &chims[t];
-            if (!chimSams.empty()) ro.chimSam = &chimSams[t];
-            if (trSAM) { ro.quantBam = &qraws[t]; ro.quantPatches = &qpatches[t]; }
-            PostMap::RangeIn ri;
-            ri.order = randomOrder ? &multOrder : nullptr; ri.merged = mg; ri.mergedRes = mgRes; ri.waspType = waspType;
-            if (waspType && hi == bt.n && lo < hi) ro.waspEnd = &waspEndOfBatch;     // (one range ends the batch)
-            errs[t] = post->processRange(bt, *r, lo, hi, ro, ri);
-            if (!bamOut) return;
-            bool cut = false;
-            if (P.outBAMcoord) for (const BamKey &k : keyss[t]) if (k.len & 0x80000000u) { cut = true; break; }
-            if (cut) {                                           // KeepPairs with both BAM files: records that belong to the sorted one only
-                std::string only; size_t pos = 0;
-                for (BamKey &k : keyss[t]) if (k.len & 0x80000000u) { k.len &= 0x7fffffffu; only.append(raw, pos, k.off - pos); pos = k.off + k.len; }
-                only.append(raw, pos, std::string::npos);
-                if (devBam) { onlys[t].swap(only); cuts[t] = 1; return; }
-                if (errs[t].empty() && !bgzfCompress(only, P.outBAMcompression, samL)) errs[t] = "EXITING because of fatal ERROR: BGZF compression failed";
-                return;
-            }
-            if (devBam) return;
-            if (errs[t].empty() && P.outBAMunsorted && !bgzfCompress(raw, P.outBAMcompression, samL)) errs[t] = "EXITING because of fatal ERROR: BGZF compression failed";
-        };
-        if (T == 1) work(0);
-        else {
-            std::atomic<uint32_t> nextR(0);
-            auto workLoop = [&] { for (;;) { const uint32_t t = nextR.fetch_add(1); if (t >= T) break; work(t); } };
-            std::vector<std::thread> th;
-            for (uint32_t w = 1; w < std::min(Wk, T); w++) th.emplace_back([&] { CpuScope cs(CPU_EMIT); workLoop(); });
-            workLoop();
-            for (auto &x : th) x.join();
+        post->drawMultOrder(*pl.bt, *pl.r, [&] { return rngUniformReal0to1(rngMultOrder); }, multOrder, pl.on.trSAM ? &nAlignT : nullptr, pl.mg, pl.mgRes);
+    }
+    // step 3, on the worker threads: one range through processRange, its BAM records compressed
+    void formatRange(EmitPlan &pl, uint32_t t) {
+        EmitRange &e = pl.ranges[t];
+        ScopedTimer tm(pl.on.timing ? &e.ms : nullptr, 1e3);
+        e.reset(pl.on.geneCounts, genes.geID.size());
+        const uint32_t lo = pl.lo(t), hi = pl.hi(t);
+        PostMap::RangeOut ro; PostMap::RangeIn ri;
+        wireRange(pl, e, false, ro, ri);
+        if (pl.waspType && hi == pl.bt->n && lo < hi) ro.waspEnd = &pl.waspEndOfBatch;     // (one range ends the batch)
+        e.err = post->processRange(*pl.bt, *pl.r, lo, hi, ro, ri);
+        if (!pl.on.bamOut) return;
+        bool cut = false;
+        if (pl.on.coordKeys) for (const BamKey &k : e.keys) if (k.len & 0x80000000u) { cut = true; break; }
+        if (cut) {                                           // KeepPairs with both BAM files: records that belong to the sorted one only
+            size_t pos = 0;
+            for (BamKey &k : e.keys) if (k.len & 0x80000000u) { k.len &= 0x7fffffffu; e.only.append(e.raw, pos, k.off - pos); pos = k.off + k.len; }
+            e.only.append(e.raw, pos, std::string::npos);
+            e.cut = true;
         }
-        auto te2 = std::chrono::steady_clock::now(); tEmitFormat += std::chrono::duration<double>(te2 - te1).count();
-        if (hostTiming && T > 0) { double mn = 1e9, mx = 0, sm = 0; for (double x : tThread) { mn = std::min(mn, x); mx = std::max(mx, x); sm += x; }
-            fprintf(stderr, "  emit: %u ranges on %u threads, section %.2f ms, per-range min %.2f / mean %.2f / max %.2f ms\n", T, std::min(Wk, T), std::chrono::duration<double, std::milli>(te2 - te1).count(), mn, sm / T, mx); }
-        struct AddTail { double &acc; std::chrono::steady_clock::time_point t0; ~AddTail() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } } addTail{tEmitTail, te2};
-        for (uint32_t t = 0; t < T; t++) if (!errs[t].empty() && error.empty()) error = errs[t];
-        // one random number per mapped read, in read order, picks the primary transcriptomic alignment (ReadAlign_quantTranscriptome.cpp:69);
-        // the flag is patched into the records (FLAG is the high half of the 5th word) before they are compressed
-        auto patchQuant = [&](uint32_t t) {
-            for (const QuantPatch &qp : qpatches[t]) {
-                uint32_t pick = randomOrder ? multOrder.quantPick[qp.ir] : (uint32_t)(int)(rngUniformReal0to1(rngMultOrder) * qp.nAlignT);
-                for (size_t k = 0; k < qp.recOffset.size(); k++) {
-                    uint8_t &hi = (uint8_t &)qraws[t][qp.recOffset[k] + 19];
-                    if (qp.recAlign[k] == pick) hi &= (uint8_t)~1u; else hi |= 1u;
-                }
+        if (pl.on.devBam) return;
+        const std::string *records = cut ? &e.only : P.outBAMunsorted ? &e.raw : nullptr;
+        if (records && e.err.empty() && !bgzfCompress(*records, P.outBAMcompression, e.sam)) e.err = "EXITING because of fatal ERROR: BGZF compression failed";
+    }
+    // one random number per mapped read, in read order, picks the primary transcriptomic alignment (ReadAlign_quantTranscriptome.cpp:69);
+    // the flag is patched into the records (FLAG is the high half of the 5th word) before they are compressed
+    void patchQuant(const EmitPlan &pl, EmitRange &e) {
+        for (const QuantPatch &qp : e.quantPatches) {
+            uint32_t pick = pl.on.randomOrder ? multOrder.quantPick[qp.ir] : (uint32_t)(int)(rngUniformReal0to1(rngMultOrder) * qp.nAlignT);
+            for (size_t k = 0; k < qp.recOffset.size(); k++) {
+                uint8_t &hi = (uint8_t &)e.quantRaw[qp.recOffset[k] + 19];
+                if (qp.recAlign[k] == pick) hi &= (uint8_t)~1u; else hi |= 1u;
             }
-        };
-        if (devBam && error.empty()) {
-            const auto td0 = std::chrono::steady_clock::now();
-            std::vector<BgzfJob> jobs;
-            if ((P.outBAMunsorted || P.outBAMcoord) && !post->samOff)
-                for (uint32_t t = 0; t < T; t++) {
-                    if (cuts[t]) jobs.push_back({&onlys[t], &o.sams[t], P.outBAMcompression});
-                    else if (P.outBAMunsorted) jobs.push_back({&o.raws[t], &o.sams[t], P.outBAMcompression});
-                }
-            if (trSAM) for (uint32_t t = 0; t < T; t++) { patchQuant(t); jobs.push_back({&qraws[t], &qzs[t], P.quantTrBAMcompression}); }
-            error = bgzfCompressDevice(jobs, P.runThreadN);
-            if (hostTiming) fprintf(stderr, "  emit: BAM records of %zu ranges compressed on the device, %.2f ms\n", jobs.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count());
         }
-        if (!error.empty()) o.used = 0;
-        { std::lock_guard<std::mutex> l(wm); fullSets.push_back(k); }
-        wcv.notify_all();
-        if (!error.empty()) return false;
-        for (uint32_t t = 0; t < T; t++) { sj.mergeFrom(sjs[t]); stats.add(sts[t]); if (quant) geneCounts.add(gcs[t]); }
-        if (hostTiming) fprintf(stderr, "  emit tail: junction records merged %.2f ms (%zu in the table)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te2).count(), sj.data.size());
-        if (trSAM) {
+    }
+    // step 4 (--gpuBAMcompression Device): the BAM records of all ranges through the device hook, before the set goes to the writer
+    void compressOnDevice(const EmitPlan &pl) {
+        const auto td0 = std::chrono::steady_clock::now();
+        std::vector<BgzfJob> jobs;
+        if (pl.on.bamOut)
+            for (uint32_t t = 0; t < pl.T; t++) {
+                EmitRange &e = pl.ranges[t];
+                if (e.cut) jobs.push_back({&e.only, &e.sam, P.outBAMcompression});
+                else if (P.outBAMunsorted) jobs.push_back({&e.raw, &e.sam, P.outBAMcompression});
+            }
+        if (pl.on.trSAM) for (uint32_t t = 0; t < pl.T; t++) { EmitRange &e = pl.ranges[t]; patchQuant(pl, e); jobs.push_back({&e.quantRaw, &e.quantZ, P.quantTrBAMcompression}); }
+        error = bgzfCompressDevice(jobs, P.runThreadN);
+        if (pl.on.timing) fprintf(stderr, "  emit: BAM records of %zu ranges compressed on the device, %.2f ms\n", jobs.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count());
+    }
+    // step 5, serial and in range order: the ranges into the run's tables and side files
+    bool foldRanges(const EmitPlan &pl, std::chrono::steady_clock::time_point te2) {
+        const EmitOutputs &on = pl.on;
+        EmitRange *const R = pl.ranges; const uint32_t T = pl.T; const ReadBatch &bt = *pl.bt;
+        for (uint32_t t = 0; t < T; t++) { sj.mergeFrom(R[t].sj); stats.add(R[t].st); if (on.geneCounts) geneCounts.add(R[t].gc); }
+        if (on.timing) fprintf(stderr, "  emit tail: junction records merged %.2f ms (%zu in the table)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te2).count(), sj.data.size());
+        if (on.trSAM)
             for (uint32_t t = 0; t < T; t++) {
-                std::string z;
-                if (!devBam) patchQuant(t);                          // (Device: patched and compressed before the hand-over above)
-                const std::string &zt = devBam ? qzs[t] : z;
-                if ((!devBam && !bgzfCompress(qraws[t], P.quantTrBAMcompression, z)) || fwrite(zt.data(), 1, zt.size(), quantOut) != zt.size()) { error = "EXITING because of fatal ERROR: could not write Aligned.toTranscriptome.out.bam"; return false; }
+                if (!on.devBam) patchQuant(pl, R[t]);                           // (Device: patched and compressed before the hand-over)
+                const std::string &z = R[t].quantZ;
+                if ((!on.devBam && !bgzfCompress(R[t].quantRaw, P.quantTrBAMcompression, R[t].quantZ)) || fwrite(z.data(), 1, z.size(), quantOut) != z.size()) { error = "EXITING because of fatal ERROR: could not write Aligned.toTranscriptome.out.bam"; return false; }
             }
-        }
-        if (chimOn && chimOut) for (uint32_t t = 0; t < T; t++) if (!chims[t].empty()) fwrite(chims[t].data(), 1, chims[t].size(), chimOut);
-        for (const std::string &cs : chimSams) if (!cs.empty()) fwrite(cs.data(), 1, cs.size(), chimSamOut);
-        if (unm) for (uint32_t t = 0; t < T; t++) for (uint32_t m = 0; m < P.dev.readNmates; m++)
-            if (!unms[t][m].empty() && unmappedOut[m]) fwrite(unms[t][m].data(), 1, unms[t][m].size(), unmappedOut[m]);
-        if (P.outBAMcoord && !post->samOff)                         // keep the records for the coordinate sort at the end of the run (in memory)
+        if (on.chim && chimOut) for (uint32_t t = 0; t < T; t++) if (!R[t].chim.empty()) fwrite(R[t].chim.data(), 1, R[t].chim.size(), chimOut);
+        if (on.chimSam) for (uint32_t t = 0; t < T; t++) if (!R[t].chimSam.empty()) fwrite(R[t].chimSam.data(), 1, R[t].chimSam.size(), chimSamOut);
+        if (on.unmapped) for (uint32_t t = 0; t < T; t++) for (uint32_t m = 0; m < P.dev.readNmates; m++)
+            if (!R[t].unmapped[m].empty() && unmappedOut[m]) fwrite(R[t].unmapped[m].data(), 1, R[t].unmapped[m].size(), unmappedOut[m]);
+        if (on.coordKeys)                                           // keep the records for the coordinate sort at the end of the run (in memory)
             for (uint32_t t = 0; t < T; t++) {
-                if (keyss[t].empty()) continue;
+                if (R[t].keys.empty()) continue;
                 uint32_t chunk = (uint32_t)coordChunks.size();
-                for (BamKey &k : keyss[t]) { k.chunk = chunk; coordKeys.push_back(k); }
-                coordChunks.emplace_back(P.outBAMunsorted ? o.raws[t] : std::move(o.raws[t]));
+                for (BamKey &k : R[t].keys) { k.chunk = chunk; coordKeys.push_back(k); }
+                coordChunks.emplace_back(P.outBAMunsorted ? R[t].raw : std::move(R[t].raw));
             }
-        if (stage1) {
+        if (on.stage1) {
             for (uint32_t t = 0; t < T; t++) {
-                sj1.mergeFrom(sj1s[t]);
-                for (uint32_t ir : helds[t])                         // held reads, in input order (ReadAlign_outputAlignments.cpp:108-121)
+                sj1.mergeFrom(R[t].sj1);
+                for (uint32_t ir : R[t].held)                        // held reads, in input order (ReadAlign_outputAlignments.cpp:108-121)
                     for (uint32_t m = 0; m < P.dev.readNmates; m++) {
                         std::string &x = heldText[m];
                         x.push_back('@'); x += bt.name(ir); x += bt.filter[ir] == 'Y' ? " 0:Y:0 " : " 0:N:0 "; x += std::to_string(bt.readIndex(ir)); x.push_back(' '); x += std::to_string(bt.fileOf(ir));
@@ -490,11 +534,38 @@ struct Runner {
             }
             if (sj1.data.size() > 4000000) sj1.collapse();
         }
-        if (waspType && !waspType->empty()) post->waspCarry = waspEndOfBatch;
-        if (writerFailed) { error = "EXITING because of fatal ERROR: could not write Aligned.out.sam"; return false; }
+        if (pl.waspType && !pl.waspType->empty()) post->waspCarry = pl.waspEndOfBatch;
+        if (writer.failed()) { error = "EXITING because of fatal ERROR: could not write Aligned.out.sam"; return false; }
         if (sj.data.size() > sjKick) sjBg.kick(sj);      // (bounded memory: ReadAlignChunk_mapChunk.cpp:66-86)
-        if (hostTiming) fprintf(stderr, "  emit: before the threads %.2f ms, threads %.2f ms, tail %.2f ms\n", std::chrono::duration<double, std::milli>(te1 - te0).count() + msBefore, std::chrono::duration<double, std::milli>(te2 - te1).count() - msBefore,
-                                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - te2).count());
+        return true;
+    }
+    bool emitBatch(const ReadBatch &bt, const staramd_results *r, const MergedBatch *mg = nullptr, const staramd_results *mgRes = nullptr, const WaspBatch *wasp = nullptr) {
+        typedef std::chrono::steady_clock Clock;
+        auto ms = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        EmitPlan pl;
+        if (!planEmit(pl, bt, r, mg, mgRes, wasp)) return false;
+        const auto te0 = Clock::now();
+        SamWriter::Set &set = writer.takeFree();
+        const auto te1 = Clock::now(); tEmitWaitSet += ms(te0, te1) * 1e-3;
+        if (set.ranges.size() < pl.T) set.ranges.resize(pl.T);
+        set.used = pl.T; pl.ranges = set.ranges.data();
+        if (pl.on.randomOrder) drawRandomOrder(pl);
+        const double msBefore = ms(te1, Clock::now());
+        pl.waspEndOfBatch = post->waspCarry;
+        overItems(pl.Wk, CPU_EMIT, pl.T, [&](size_t t) { formatRange(pl, (uint32_t)t); });
+        const auto te2 = Clock::now(); tEmitFormat += ms(te1, te2) * 1e-3;
+        if (pl.on.timing) {
+            double mn = 1e9, mx = 0, sm = 0;
+            for (uint32_t t = 0; t < pl.T; t++) { const double x = pl.ranges[t].ms; mn = std::min(mn, x); mx = std::max(mx, x); sm += x; }
+            fprintf(stderr, "  emit: %u ranges on %u threads, section %.2f ms, per-range min %.2f / mean %.2f / max %.2f ms\n", pl.T, std::min(pl.Wk, pl.T), ms(te1, te2), mn, sm / pl.T, mx);
+        }
+        ScopedTimer tail(&tEmitTail, 1.0, te2);
+        for (uint32_t t = 0; t < pl.T; t++) if (!pl.ranges[t].err.empty() && error.empty()) error = pl.ranges[t].err;
+        if (pl.on.devBam && error.empty()) compressOnDevice(pl);
+        if (!error.empty()) set.used = 0;
+        writer.handOver(set);
+        if (!error.empty() || !foldRanges(pl, te2)) return false;
+        if (pl.on.timing) fprintf(stderr, "  emit: before the threads %.2f ms, threads %.2f ms, tail %.2f ms\n", ms(te0, te1) + msBefore, ms(te1, te2) - msBefore, ms(te2, Clock::now()));
         return true;
     }
     // Aligned.sortedByCoord.out.bam (BAMbinSortByCoordinate.cpp, BAMbinSortUnmapped.cpp): mapped records by (refID << 32 | pos, read order,
@@ -520,17 +591,14 @@ struct Runner {
         if (dev && n > 0 && !bgzfDeviceInstalled()) { if (!toStdout) fclose(f); return BGZF_DEVICE_MISSING; }
         std::string devErr;
         for (uint64_t base = 0; base < n && !failed; base += per * T) {
-            std::vector<std::string> outS(T), raws(dev ? T : 0); std::vector<std::thread> th;
-            auto work = [&](uint64_t t) {
+            std::vector<std::string> outS(T), raws(dev ? T : 0);
+            onThreads(T, CPU_NONE, [&](size_t t) {
                 uint64_t lo = std::min(n, base + t * per), hi = std::min(n, lo + per);
                 std::string raw;
                 for (uint64_t i = lo; i < hi; i++) { const BamKey &k = K[ord[i]]; raw.append(coordChunks[k.chunk], k.off, k.len); }
                 if (dev) raws[t].swap(raw);
                 else if (!bgzfCompress(raw, P.outBAMcompression, outS[t])) failed = true;
-            };
-            for (uint64_t t = 1; t < T; t++) th.emplace_back(work, t);
-            work(0);
-            for (auto &x : th) x.join();
+            });
             if (dev) {
                 std::vector<BgzfJob> jobs;
                 for (uint64_t t = 0; t < T; t++) jobs.push_back({&raws[t], &outS[t], P.outBAMcompression});
@@ -551,7 +619,6 @@ struct Runner {
         if (!devErr.empty()) return devErr;
         return failed ? "EXITING because of fatal ERROR: could not write " + path : "";
     }
-    bool emit(const staramd_results *r, const staramd_results *rMerged = nullptr) { return emitBatch(batch, r, P.peOverlapNbasesMin > 0 && P.dev.readNmates == 2 ? &mergedMain : nullptr, rMerged, P.wasp ? &waspMain : nullptr); }
     // end of the 1st pass (twoPassRunPass1.cpp:75-96): junctions + Log.final.out of the pass into _STARpass1/, insertion of the
     // junctions into the index, reads rewound.  The caller then re-uploads the index (staramd_update_index).
     bool endPass1() {
@@ -605,7 +672,7 @@ struct Runner {
         sjBg.drainInto(sj);
         if (!P.outSJnone) sjThread = std::thread([&] { sjError = sj.filterAndWrite(P, gi, P.outFileNamePrefix + "SJ.out.tab", bySJoutStage == 2); });
         struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } joinSj{sjThread};
-        stopWriter();
+        writer.stop();
         for (FILE *&u : unmappedOut) if (u) { fclose(u); u = nullptr; }
         if (chimSamOut) { fclose(chimSamOut); chimSamOut = nullptr; }
         if (quantOut) { std::string e; bgzfEof(e); fwrite(e.data(), 1, e.size(), quantOut); if (quantOut == stdout) fflush(stdout); else fclose(quantOut); quantOut = nullptr; }
@@ -615,9 +682,9 @@ struct Runner {
                         (unsigned long long)stats.mappedReadsU, (unsigned long long)stats.mappedReadsM);
             fclose(chimOut); chimOut = nullptr;
         }
-        if (writerFailed) { error = "EXITING because of fatal ERROR: could not write Aligned.out.sam"; return false; }
+        if (writer.failed()) { error = "EXITING because of fatal ERROR: could not write Aligned.out.sam"; return false; }
         if (samOut) {
-            if (samFd >= 0) { fflush(samOut); fseeko(samOut, (off_t)samPos, SEEK_SET); }      // the batches went out through positional writes: the stream goes on behind them
+            writer.resumeStream();
             if (P.outBAMunsorted) { std::string e; bgzfEof(e); fwrite(e.data(), 1, e.size(), samOut); }
             if (samOut == stdout) fflush(stdout); else fclose(samOut);
             samOut = nullptr;
@@ -631,7 +698,7 @@ struct Runner {
         if (P.quantGeneCounts) { error = geneCounts.write(P.outFileNamePrefix + "ReadsPerGene.out.tab", genes, stats); if (!error.empty()) return false; }
         return true;
     }
-    ~Runner() { stopWriter(); if (getenv("STARAMD_HOST_TIMING")) fprintf(stderr, "  host stages, whole run: writer %.3f s, emit: wait for a text buffer set %.3f s, format on threads %.3f s, serial tail %.3f s\n", tWriter, tEmitWaitSet, tEmitFormat, tEmitTail); if (samOut && samOut != stdout) fclose(samOut); if (quantOut == stdout) quantOut = nullptr; for (FILE *u : unmappedOut) if (u) fclose(u); if (chimOut) fclose(chimOut); if (quantOut) fclose(quantOut); }
+    ~Runner() { writer.stop(); if (getenv("STARAMD_HOST_TIMING")) fprintf(stderr, "  host stages, whole run: writer %.3f s, emit: wait for a text buffer set %.3f s, format on threads %.3f s, serial tail %.3f s\n", writer.seconds, tEmitWaitSet, tEmitFormat, tEmitTail); if (samOut && samOut != stdout) fclose(samOut); if (quantOut == stdout) quantOut = nullptr; for (FILE *u : unmappedOut) if (u) fclose(u); if (chimOut) fclose(chimOut); if (quantOut) fclose(quantOut); }
 };
 
 } // namespace staramd
@@ -664,9 +731,8 @@ void sah_set_sjdb_resident_fn(int (*fn)(void *, const staramd_sjdb_args *, stara
 int sah_chim_select_on_device(void *h) {
     Runner *r = (Runner *)h;
     staramd::RunParams &P = r->P;
-    const bool mergedMates = P.peOverlapNbasesMin > 0 && P.dev.readNmates == 2;
     // (chimSegmentMinPositive is 0 during the 1st pass of a 2-pass run -- twoPassRunPass1.cpp:24 -- and comes back with the 2nd: the choice is made once, for the run)
-    if (!(P.chim.segmentMin > 0 && P.chim.multimapNmax == 0 && !mergedMates && P.dev.resultSelect == 0)) return 0;
+    if (!(P.chim.segmentMin > 0 && P.chim.multimapNmax == 0 && !P.mergedMates() && P.dev.resultSelect == 0)) return 0;
     P.dev.resultSelect = 2;
     return 1;
 }
@@ -700,84 +766,44 @@ int sah_bgzf_on_device(void *h) { return ((Runner *)h)->P.gpuBAMdevice ? 1 : 0; 
 double sah_genome_load_seconds(void *h) { return ((Runner *)h)->gi.loadSeconds; }
 void sah_cpu_add(int stage, uint64_t ns) { staramd::cpuAdd(stage, ns); }
 void sah_cpu_seconds(double out[8], int reset) { for (int i = 0; i < staramd::CPU_NSTAGE; i++) out[i] = (double)staramd::cpuTake(i, reset != 0) * 1e-9; }
-void sah_fast_path_counts(void *h, uint64_t out[2]) { Runner *r = (Runner *)h; out[0] = r->nMappedWrites; out[1] = r->reader.mappedBatches.load(); }
-void sah_emit_seconds(void *h, double out[4]) { Runner *r = (Runner *)h; out[0] = r->tEmitWaitSet; out[1] = r->tEmitFormat; out[2] = r->tEmitTail; out[3] = r->tWriter; }
-int sah_next_batch(void *h, uint64_t maxReads, staramd_batch *out) {
-    Runner *r = (Runner *)h;
-    int n = r->nextBatch(maxReads);
-    if (n > 0 && out) *out = r->batchView;
-    return n;
-}
-int sah_emit(void *h, const staramd_results *res) { return ((Runner *)h)->emit(res) ? 0 : -1; }
+void sah_fast_path_counts(void *h, uint64_t out[2]) { Runner *r = (Runner *)h; out[0] = r->writer.mappedWrites; out[1] = r->reader.mappedBatches.load(); }
+void sah_emit_seconds(void *h, double out[4]) { Runner *r = (Runner *)h; out[0] = r->tEmitWaitSet; out[1] = r->tEmitFormat; out[2] = r->tEmitTail; out[3] = r->writer.seconds; }
+// ---- batch operations.  Every one exists for the main batch (one batch at a time: sah_next_batch, map, sah_emit) and for a slot of the pipelined variant (star_amd CLI:
+// FASTQ parsing of batch k+1, the device mapping of batch k and the post-map / SAM writing of batch k-1 overlap; parse and emit are each called from ONE thread, in
+// batch order).  Both forward to one member function of Runner with their batch set and the error string of their stage.
+int sah_next_batch(void *h, uint64_t maxReads, staramd_batch *out) { Runner *r = (Runner *)h; return r->parseBatch(r->mainSet, maxReads, out, r->error); }
+int sah_parse_slot(void *h, int slot, uint64_t maxReads, staramd_batch *out) { Runner *r = (Runner *)h; return r->parseBatch(r->slots[slot], maxReads, out, r->parseError); }
+int sah_emit(void *h, const staramd_results *res) { Runner *r = (Runner *)h; return r->emitSet(r->mainSet, res, nullptr) ? 0 : -1; }
 // --peOverlapNbasesMin > 0: after sah_next_batch, sah_merged_batch gives the pairs of the batch whose mates overlap, merged into single reads (0 = none);
 // map them with the same engine and hand both result sets to sah_emit_merged.  Same for the slots of the pipelined variant.
-int sah_merged_batch(void *h, staramd_batch *out) { Runner *r = (Runner *)h; if (!(r->P.peOverlapNbasesMin > 0 && r->P.dev.readNmates == 2) || r->mergedMain.reads.n == 0) return 0; if (out) *out = r->mergedMain.reads.view(); return (int)r->mergedMain.reads.n; }
-int sah_emit_merged(void *h, const staramd_results *res, const staramd_results *resMerged) { return ((Runner *)h)->emit(res, resMerged) ? 0 : -1; }
+int sah_merged_batch(void *h, staramd_batch *out) { Runner *r = (Runner *)h; return r->mergedBatch(r->mainSet, out); }
+int sah_merged_slot(void *h, int slot, staramd_batch *out) { Runner *r = (Runner *)h; return r->mergedBatch(r->slots[slot], out); }
+int sah_emit_merged(void *h, const staramd_results *res, const staramd_results *resMerged) { Runner *r = (Runner *)h; return r->emitSet(r->mainSet, res, resMerged) ? 0 : -1; }
+int sah_emit_slot_merged(void *h, int slot, const staramd_results *res, const staramd_results *resMerged) { Runner *r = (Runner *)h; return r->emitSet(r->slots[slot], res, resMerged) ? 0 : -1; }
+// (a slot emitted without results of merged mates: the caller found none -- sah_merged_slot -- and nothing is asked of the slot's merged batch)
+int sah_emit_slot(void *h, int slot, const staramd_results *res) { Runner *r = (Runner *)h; return r->emitSet(r->slots[slot], res, nullptr, false) ? 0 : -1; }
 // --waspOutputMode SAMtag: after mapping a batch, sah_wasp_batch builds from its results the allele-swapped reads that WASP maps again (0 = none, still call
-// sah_wasp_results with NULL); map them with the same engine, hand the results to sah_wasp_results, then emit as usual.  *_slot: the pipelined variant.
-int sah_wasp_batch(void *h, const staramd_results *res, staramd_batch *out) {
-    Runner *r = (Runner *)h;
-    if (!r->P.wasp || r->pass1) return 0;
-    r->waspMain.build(r->P, r->gi, r->variation, r->batch, *res);
-    if (out) *out = r->waspMain.reads.view();
-    return (int)r->waspMain.reads.n;
-}
-int sah_wasp_results(void *h, const staramd_results *res, const staramd_results *resWasp) {
-    Runner *r = (Runner *)h;
-    if (!r->P.wasp || r->pass1) return 0;
-    if (r->waspMain.reads.n > 0 && !resWasp) { r->error = "EXITING because of FATAL ERROR: --waspOutputMode: results of the re-mapped reads are missing"; return -1; }
-    if (r->waspMain.reads.n > 0) r->waspMain.finish(r->P, r->batch, *res, *resWasp);
-    return 0;
-}
-int sah_wasp_slot(void *h, int slot, const staramd_results *res, staramd_batch *out) {
-    Runner *r = (Runner *)h;
-    if (!r->P.wasp || r->pass1) return 0;
-    r->waspSlots[slot].build(r->P, r->gi, r->variation, r->slots[slot], *res);
-    if (out) *out = r->waspSlots[slot].reads.view();
-    return (int)r->waspSlots[slot].reads.n;
-}
-int sah_wasp_results_slot(void *h, int slot, const staramd_results *res, const staramd_results *resWasp) {
-    Runner *r = (Runner *)h;
-    if (!r->P.wasp || r->pass1) return 0;
-    if (r->waspSlots[slot].reads.n > 0) { if (!resWasp) { std::lock_guard<std::mutex> l(r->errM); r->mapError = "EXITING because of FATAL ERROR: --waspOutputMode: results of the re-mapped reads are missing"; return -1; } r->waspSlots[slot].finish(r->P, r->slots[slot], *res, *resWasp); }
-    return 0;
-}
-int sah_merged_slot(void *h, int slot, staramd_batch *out) { Runner *r = (Runner *)h; if (!(r->P.peOverlapNbasesMin > 0 && r->P.dev.readNmates == 2) || r->mergedSlots[slot].reads.n == 0) return 0; if (out) *out = r->mergedSlots[slot].reads.view(); return (int)r->mergedSlots[slot].reads.n; }
-int sah_emit_slot_merged(void *h, int slot, const staramd_results *res, const staramd_results *resMerged) {
-    Runner *r = (Runner *)h;
-    return r->emitBatch(r->slots[slot], res, r->P.peOverlapNbasesMin > 0 && r->P.dev.readNmates == 2 ? &r->mergedSlots[slot] : nullptr, resMerged, r->P.wasp ? &r->waspSlots[slot] : nullptr) ? 0 : -1;
-}
-// pipelined variant (star_amd CLI): three batch slots so that FASTQ parsing of batch k+1, the device mapping of batch k and
-// the post-map / SAM writing of batch k-1 overlap.  parse and emit are each called from ONE thread, in batch order.
-int sah_parse_slot(void *h, int slot, uint64_t maxReads, staramd_batch *out) {
-    Runner *r = (Runner *)h;
-    std::string err;
-    bool ok = r->reader.nextBatch(r->slots[slot], r->P, maxReads, err);
-    if (!err.empty()) { std::lock_guard<std::mutex> l(r->errM); r->parseError = err; return -1; }
-    if (!ok) return 0;
-    if (out) *out = r->slots[slot].view();
-    if (r->P.peOverlapNbasesMin > 0 && r->P.dev.readNmates == 2) r->mergedSlots[slot].build(r->slots[slot], r->P);
-    return (int)r->slots[slot].n;
-}
+// sah_wasp_results with NULL); map them with the same engine, hand the results to sah_wasp_results, then emit as usual.  *_slot: the pipelined variant, on the mapper threads.
+int sah_wasp_batch(void *h, const staramd_results *res, staramd_batch *out) { Runner *r = (Runner *)h; return r->waspBatch(r->mainSet, res, out); }
+int sah_wasp_slot(void *h, int slot, const staramd_results *res, staramd_batch *out) { Runner *r = (Runner *)h; return r->waspBatch(r->slots[slot], res, out); }
+int sah_wasp_results(void *h, const staramd_results *res, const staramd_results *resWasp) { Runner *r = (Runner *)h; return r->waspResults(r->mainSet, res, resWasp, r->error); }
+int sah_wasp_results_slot(void *h, int slot, const staramd_results *res, const staramd_results *resWasp) { Runner *r = (Runner *)h; return r->waspResults(r->slots[slot], res, resWasp, r->mapError); }
 // page-locked (or any other) memory for the numeric arrays of the batches; call once, before the first batch is parsed and never with batches alive
 void sah_set_batch_alloc(void *(*alloc)(uint64_t), void (*release)(void *)) { staramd::g_batchAllocFn = alloc; staramd::g_batchFreeFn = release; }
 int sah_fill_slot(void *h, int slot, uint64_t maxReads) {
     Runner *r = (Runner *)h;
     std::string err;
-    bool ok = r->reader.fillBatch(r->slots[slot], r->P, maxReads, err);
-    if (!err.empty()) { std::lock_guard<std::mutex> l(r->errM); r->parseError = err; return -1; }
-    return ok ? (int)r->slots[slot].n : 0;
+    bool ok = r->reader.fillBatch(r->slots[slot].batch, r->P, maxReads, err);
+    if (!err.empty()) { r->report(r->parseError, err); return -1; }
+    return ok ? (int)r->slots[slot].batch.n : 0;
 }
 int sah_convert_slot(void *h, int slot, staramd_batch *out) {
     Runner *r = (Runner *)h;
     std::string err;
-    bool ok = r->reader.convertBatch(r->slots[slot], r->P, err);
-    if (!ok || !err.empty()) { std::lock_guard<std::mutex> l(r->errM); r->parseError = err.empty() ? "convertBatch failed" : err; return -1; }
-    if (out) *out = r->slots[slot].view();
-    if (r->P.peOverlapNbasesMin > 0 && r->P.dev.readNmates == 2) r->mergedSlots[slot].build(r->slots[slot], r->P);
-    return (int)r->slots[slot].n;
+    bool ok = r->reader.convertBatch(r->slots[slot].batch, r->P, err);
+    if (!ok || !err.empty()) { r->report(r->parseError, err.empty() ? "convertBatch failed" : err); return -1; }
+    return r->converted(r->slots[slot], out);
 }
-int sah_emit_slot(void *h, int slot, const staramd_results *res) { Runner *r = (Runner *)h; return r->emitBatch(r->slots[slot], res, nullptr, nullptr, r->P.wasp ? &r->waspSlots[slot] : nullptr) ? 0 : -1; }
 int sah_threads(void *h) { return ((Runner *)h)->P.runThreadN; }
 // 2-pass mapping: sah_in_pass1() is 1 after sah_create when --twopassMode Basic was given; map all batches, call sah_pass1_end()
 // (junction insertion on the host), re-upload sah_genome()/sah_params() with staramd_update_index(), map all batches again.

@@ -174,9 +174,7 @@ static std::string sjdbPrepareAndBuild(const RunParams &P, GenomeIndex &gi, cons
     {
         const int T = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(P.runThreadN, 1), V.nGenome >> 24));
         const uint64_t per = (V.nGenome + T - 1) / T;
-        std::vector<std::thread> th;
-        for (int t = 0; t < T; t++) th.emplace_back([&, t] { const uint64_t lo = std::min<uint64_t>(V.nGenome, (uint64_t)t * per), hi = std::min<uint64_t>(V.nGenome, lo + per); if (hi > lo) memcpy(Gp.data() + GP + lo, gi.G.data() + lo, hi - lo); });
-        for (auto &x : th) x.join();
+        onThreads((size_t)T, CPU_NONE, [&](size_t t) { const uint64_t lo = std::min<uint64_t>(V.nGenome, (uint64_t)t * per), hi = std::min<uint64_t>(V.nGenome, lo + per); if (hi > lo) memcpy(Gp.data() + GP + lo, gi.G.data() + lo, hi - lo); });
     }
     const uint8_t *G = Gp.data() + GP;
     const std::vector<uint64_t> oldStart = gi.sjdbStart, oldEnd = gi.sjdbEnd;
@@ -369,10 +367,7 @@ static std::string sjdbPrepareAndBuild(const RunParams &P, GenomeIndex &gi, cons
                 }
             }
         };
-        std::vector<std::thread> th;
-        for (int t = 1; t < T; t++) th.emplace_back(work, t);
-        work(0);
-        for (auto &x : th) x.join();
+        onThreads((size_t)T, CPU_NONE, work);
         size_t tot = 0; for (auto &p : part) tot += p.size();
         ind.reserve(tot + 1);
         for (auto &p : part) ind.insert(ind.end(), p.begin(), p.end());
@@ -433,12 +428,7 @@ static std::string sjdbPrepareAndBuild(const RunParams &P, GenomeIndex &gi, cons
                 emit(oldEntry(isa));
             }
         };
-        {
-            std::vector<std::thread> th;
-            for (int t = 1; t < T; t++) th.emplace_back(slice, t);
-            slice(0);
-            for (auto &x : th) x.join();
-        }
+        onThreads((size_t)T, CPU_NONE, slice);
         for (auto &dv : deferred) for (const T2 &e : dv) SA2.put(e[0], e[1]);
         uint64_t isa2 = oldNSA + cutJ[T];
         for (uint64_t isj = cutJ[T]; isj < nInd; isj++) SA2.put(isa2++, sjEntry(ind[isj][1]));     // suffixes larger than every old one

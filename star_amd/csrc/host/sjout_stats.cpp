@@ -47,7 +47,7 @@ void OutSJ::collapse() {
     // counting scatter, the input cut into T slices
     std::vector<std::vector<size_t>> cnt(T, std::vector<size_t>(T + 1, 0));
     std::vector<uint8_t> rng(n);
-    auto each = [&](const std::function<void(unsigned)> &f) { std::vector<std::thread> th; for (unsigned t = 1; t < T; t++) th.emplace_back(f, t); f(0); for (auto &x : th) x.join(); };
+    auto each = [&](const std::function<void(unsigned)> &f) { onThreads(T, CPU_NONE, f); };
     each([&](unsigned t) { std::vector<size_t> c(T + 1, 0); for (size_t i = n * t / T; i < n * (t + 1) / T; i++) { unsigned r = rangeOf(data[i]); rng[i] = (uint8_t)r; c[r]++; } cnt[t] = c; });
     std::vector<size_t> rangeStart(T + 1, 0);
     for (unsigned r = 0; r < T; r++) { size_t tot = 0; for (unsigned t = 0; t < T; t++) { size_t c = cnt[t][r]; cnt[t][r] = rangeStart[r] + tot; tot += c; } rangeStart[r + 1] = rangeStart[r] + tot; }

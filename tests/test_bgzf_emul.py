@@ -454,13 +454,35 @@ def run_with_bgzf(info, prefix, engine_factory, bz, batch_reads=777):
 @pytest.mark.parametrize("types", [["Unsorted"], ["Unsorted", "SortedByCoordinate"]])
 def test_host_run_device_mode_emulated(bz, types, tmp_path, built):
     """--gpuBAMcompression Device through the hook, the emulated compressor behind it: the decompressed files equal the Host run's"""
+    _device_mode_case(bz, test_golden._tiny_info(), types, tmp_path)
+
+
+@pytest.mark.skipif(not refstar.have_ref(), reason="oracle/_ref/STAR not built (no /root/reference here)")
+def test_host_run_device_mode_emulated_sorted_only_records(bz, tmp_path, built):
+    """KeepPairs with both BAM files on reads that have one-mate alignments (the data of test_host_flags.test_keep_pairs: the 2nd mate of every 3rd pair
+    is junk): the sorted file gets records that the unsorted one does not, and the device path has to be handed the unsorted file's records without them"""
+    import test_host_flags
+    info = test_host_flags._multicopy(tmp_path, seed=22)
+    lines = open(info["fastq"][1]).read().split("\n")
+    for i in range(0, len(lines) // 4, 3):
+        lines[4 * i + 1] = ("ACGTTGCATGCCGATATCGGCTAGCTAGGATCCGATTTAGGCTCTAGAGCTCGATCGGGATATCCGCGATATTAGCAGCTACGACTAGCATCGACTAGC" * 3)[i % 7:i % 7 + len(lines[4 * i + 1])]
+    junk = str(tmp_path / "junk_2.fq")
+    open(junk, "w").write("\n".join(lines))
+    info["fastq"] = [info["fastq"][0], junk]
+    info["extra"] = ["--outFilterMultimapNmax", "50", "--outFilterMultimapScoreRange", "4", "--outFilterScoreMinOverLread", "0.3", "--outFilterMatchNminOverLread", "0.3"]
+    outs = _device_mode_case(bz, info, ["Unsorted", "SortedByCoordinate"], tmp_path)
+    assert len(bam_parts(outs["Device"] + "Aligned.out.bam")[2]) != len(bam_parts(outs["Device"] + "Aligned.sortedByCoord.out.bam")[2])      # (the case does occur in these reads)
+
+
+def _device_mode_case(bz, info0, types, tmp_path):
     outs = {}
     for mode in ("Host", "Device"):
-        info = dict(test_golden._tiny_info())
-        info["extra"] = ["--outSAMtype", "BAM"] + types + ["--outSAMunmapped", "Within", "KeepPairs", "--runThreadN", "3", "--gpuBAMcompression", mode]
+        info = dict(info0)
+        info["extra"] = list(info.get("extra", [])) + ["--outSAMtype", "BAM"] + types + ["--outSAMunmapped", "Within", "KeepPairs", "--runThreadN", "3", "--gpuBAMcompression", mode]
         outs[mode] = run_with_bgzf(info, str(tmp_path / mode) + "_", lambda g, p: oracle_lib.Oracle(g, p), bz if mode == "Device" else None, batch_reads=300)
     for f in ["Aligned.out.bam"] + (["Aligned.sortedByCoord.out.bam"] if "SortedByCoordinate" in types else []):
         h, d = open(outs["Host"] + f, "rb").read(), open(outs["Device"] + f, "rb").read()
         assert d[-28:] == EOF_MARK
         assert same_bam(outs["Device"] + f, outs["Host"] + f), f
         assert d != h, "the records were not compressed by the device path"
+    return outs

@@ -38,6 +38,18 @@ def test_by_sjout_oracle(name, case, tmp_path, built):
     _case(name, CASES[case], tmp_path, lambda g, p: oracle_lib.Oracle(g, p))
 
 
+def test_by_sjout_held_reads_keep_input_order(tmp_path, built):
+    """the reads held in stage 1 reach stage 2 in input order however many ranges a batch is cut into: the SAM records of a run with 3 ranges per
+    batch (batches of 1000 reads, at least 256 reads per range) are those of a run whose batches are one range each (300 reads), line for line"""
+    body = {}
+    for threads, batch in (("1", 300), ("3", 1000)):
+        info = dict(prepare("pe101", str(tmp_path), need_ref=False))
+        info["extra"] = list(info["extra"]) + ["--outFilterType", "BySJout", "--runThreadN", threads]
+        new = run_with_engine(info, os.path.join(os.path.dirname(info["fastq"][0]), "t%s_" % threads), lambda g, p: oracle_lib.Oracle(g, p), batch_reads=batch)
+        body[threads] = [l for l in open(new + "Aligned.out.sam", "rb") if not l.startswith(b"@")]
+    assert len(body["1"]) > 1000 and body["3"] == body["1"]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,case", [("pe101", "plain"), ("pe101", "two_pass"), ("pe150_indel", "encode"), ("se50", "plain")])
 def test_by_sjout_engine(name, case, tmp_path, built):

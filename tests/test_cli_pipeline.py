@@ -141,7 +141,7 @@ def test_cli_pipeline_wasp_verdict_on_chimeric_bam_records(batch, tmp_path, buil
 
 def test_sam_into_a_named_pipe(tmp_path, built):
     """Aligned.out.sam as a FIFO (mkfifo + a consumer, the way it is piped into samtools): the writer thread must fall back to sequential writes -- a
-    positional write on a pipe fails with ESPIPE (runner.cpp writerLoop)"""
+    positional write on a pipe fails with ESPIPE (runner.cpp SamWriter)"""
     import threading
     info = dict(prepare("pe101", str(tmp_path), need_ref=False))
     d = os.path.dirname(info["fastq"][0])

@@ -1,5 +1,5 @@
 // writer_bench: how fast does ONE file on this file system take the SAM text of a run?  (g++ -O2 -pthread tools/writer_bench.cpp -o /tmp/writer_bench)
-// The SAM writer of the front end (star_amd/csrc/host/runner.cpp: writerLoop) appends ~230 MB per batch of 400 k pairs to Aligned.out.sam; on the GPU boxes
+// The SAM writer of the front end (star_amd/csrc/host/runner.cpp: SamWriter) appends ~230 MB per batch of 400 k pairs to Aligned.out.sam; on the GPU boxes
 // the output directory is tmpfs and the writer, not the GPU, set the step of the pipeline.  This program replays the writer's access pattern without the rest:
 // B batches of S bytes from R source buffers (the per-range text buffers of the formatting threads), by one of the methods below, W threads.
 //   pwrite      W threads, each range at its offset (serialised by the inode lock)
