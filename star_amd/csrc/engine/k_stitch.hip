@@ -6,7 +6,7 @@
 //   stitchAlignToTranscript source/stitchAlignToTranscript.cpp:9-415 gap fill, junction / indel placement, sjdb scoring
 //   extendAlign             source/extendAlign.cpp:6-93
 //   binarySearch2           source/binarySearch2.cpp:3-43
-//   blocksOverlap           source/blocksOverlap.cpp:3-40
+//   blocksOverlap           source/blocksOverlap.cpp:3-40           (../chim_pair.h, shared with the host)
 //
 // Mapping: ONE WAVEFRONT PER WINDOW, all 64 lanes cooperating.
 //   * The include/exclude recursion is an explicit depth-first walk over ONE working transcript with an undo log
@@ -451,21 +451,6 @@ template <class T> __device__ __forceinline__ void ldsPut(LDS T *p, const T &v) 
     LDS u32 *d = (LDS u32 *)p; const u32 *s = (const u32 *)&v;
 #pragma unroll
     for (u32 i = 0; i < sizeof(T) / 4; i++) d[i] = s[i];
-}
-
-// blocksOverlap.cpp:3-40 on two exon lists in the output record format (run by one lane)
-template <class P1, class P2> __device__ static u32 blocksOverlap(P1 e1, u32 n1, P2 e2, u32 n2) {
-    u32 i1 = 0, i2 = 0, nOverlap = 0;
-    while (i1 < n1 && i2 < n2) {
-        u64 rs1 = e1[i1].R, rs2 = e2[i2].R;
-        u64 re1 = rs1 + e1[i1].L, re2 = rs2 + e2[i2].L;
-        u64 gs1 = e1[i1].G, gs2 = e2[i2].G;
-        if (rs1 >= re2) i2++;
-        else if (rs2 >= re1) i1++;
-        else if (gs1 - rs1 != gs2 - rs2) { if (re1 >= re2) i2++; if (re2 >= re1) i1++; }
-        else { nOverlap += (u32)(min(re1, re2) - max(rs1, rs2)); if (re1 >= re2) i2++; if (re2 >= re1) i1++; }
-    }
-    return nOverlap;
 }
 
 // transcripts recorded for the current window: records in the OUTPUT format (staramd_transcript followed by its
@@ -1303,22 +1288,6 @@ extern "C" __global__ void __launch_bounds__(256) k_stitch_verify(const DevIndex
 // ReadAlign_chimericDetectionOld.cpp:50-108 over the records of the pools: trBest against the head of every other window and the other transcripts of its own.  One lane
 // per read (k_stitch_finish); the arithmetic is the reference's (unsigned 64-bit read coordinates, the `roStart > readLength[0]` step over the mate spacer).
 struct ChimSel { i32 scoreBest, scoreNext; u32 strBest; u32 win, rank; bool have; };       // win: index among the read's windows (winOffset + win), rank inside it
-__device__ __forceinline__ u32 chimStrOf(const staramd_transcript &t) {                      // :40-46, :59-65
-    if (t.intronMotifs[1] == 0 && t.intronMotifs[2] == 0) return 0u;
-    return ((t.Str == 0) == (t.intronMotifs[1] > 0)) ? 1u : 2u;
-}
-// blocksOverlap.cpp:3-41 on two transcripts of the pools (ea / eb: their first exons)
-__device__ static u64 chimBlocksOverlap(const staramd_transcript &a, const staramd_exon *ea, const staramd_transcript &b, const staramd_exon *eb) {
-    u32 i1 = 0, i2 = 0; u64 n = 0;
-    while (i1 < a.nExons && i2 < b.nExons) {
-        const u64 rs1 = ea[i1].R, rs2 = eb[i2].R, re1 = rs1 + ea[i1].L, re2 = rs2 + eb[i2].L, gs1 = ea[i1].G, gs2 = eb[i2].G;
-        if (rs1 >= re2) i2++;
-        else if (rs2 >= re1) i1++;
-        else if (gs1 - rs1 != gs2 - rs2) { if (re1 >= re2) i2++; if (re2 >= re1) i1++; }
-        else { n += min(re1, re2) - max(rs1, rs2); if (re1 >= re2) i2++; if (re2 >= re1) i1++; }
-    }
-    return n;
-}
 __device__ static ChimSel chimSelectPartner(const staramd_params &P, const DevBatch &B, const DRead &rd, u32 ir, u32 bestWin) {
     ChimSel c; c.scoreBest = 0; c.scoreNext = 0; c.strBest = 0; c.win = 0; c.rank = 0; c.have = false;
     const u64 Lread = B.readOffset[ir + 1] - B.readOffset[ir], len0 = B.mate1Length[ir];
@@ -1326,35 +1295,25 @@ __device__ static ChimSel chimSelectPartner(const staramd_params &P, const DevBa
     const staramd_transcript tb = B.trPool[ob.trOffset];
     const staramd_exon *xb = B.exPool + ob.exOffset + tb.exonOffset;
     const u32 nb = tb.nExons;
-    u64 roStart1 = tb.Str == 0 ? (u64)xb[0].R : Lread - xb[nb - 1].R - xb[nb - 1].L;
-    u64 roEnd1 = tb.Str == 0 ? (u64)xb[nb - 1].R + xb[nb - 1].L - 1 : Lread - xb[0].R - 1;
-    if (roStart1 > len0) roStart1--;
-    if (roEnd1 > len0) roEnd1--;
-    const u32 chimStr = chimStrOf(tb);
-    const u64 segMin = P.chimSegmentMin, gapMax = P.chimSegmentReadGapMax;
+    const ChimExtent e1 = chimExtent(tb.Str, xb[0], xb[nb - 1], Lread, len0);
+    const u32 chimStr = chimMotifStrand(tb.Str, tb.intronMotifs, false);
     for (u32 w = 0; w < rd.nWin; w++) {
         const DWinOut o = B.wout[rd.winOffset + w];
         const u32 nt = w == bestWin ? o.nTr : min(o.nTr, 1u);                       // other windows: their head only (:52)
         for (u32 k = (w == bestWin ? 1u : 0u); k < nt; k++) {                       // the best window: everything but trBest itself (:53)
             const staramd_transcript t = B.trPool[o.trOffset + k];
             if (t.intronMotifs[0] > 0) continue;
-            const u32 chimStr1 = chimStrOf(t);
+            const u32 chimStr1 = chimMotifStrand(t.Str, t.intronMotifs, false);
             if (chimStr != 0 && chimStr1 != 0 && chimStr != chimStr1) continue;
             const staramd_exon *x = B.exPool + o.exOffset + t.exonOffset; const u32 ne = t.nExons;
-            u64 roStart2 = t.Str == 0 ? (u64)x[0].R : Lread - x[ne - 1].R - x[ne - 1].L;
-            u64 roEnd2 = t.Str == 0 ? (u64)x[ne - 1].R + x[ne - 1].L - 1 : Lread - x[0].R - 1;
-            if (roStart2 > len0) roStart2--;
-            if (roEnd2 > len0) roEnd2--;
-            const u64 chimOverlap = roStart2 > roStart1 ? (roStart2 > roEnd1 ? 0 : roEnd1 - roStart2 + 1) : (roEnd2 < roStart1 ? 0 : roEnd2 - roStart1 + 1);
-            const bool diffMates = (roEnd1 < len0 && roStart2 >= len0) || (roEnd2 < len0 && roStart1 >= len0);
-            if (!(roEnd1 > segMin + roStart1 + chimOverlap && roEnd2 > segMin + roStart2 + chimOverlap
-                  && (diffMates || ((roEnd1 + gapMax + 1) >= roStart2 && (roEnd2 + gapMax + 1) >= roStart1)))) continue;
+            u64 chimOverlap;
+            if (!chimPairEligible(e1, chimExtent(t.Str, x[0], x[ne - 1], Lread, len0), len0, P.chimSegmentMin, P.chimSegmentReadGapMax, chimOverlap)) continue;
             const i32 chimScore = tb.maxScore + t.maxScore - (i32)chimOverlap;
             u64 overlap1 = 0;
             if (k > 0 && c.scoreBest > 0) {                                         // :84-88 (only ever non-zero for two transcripts of one window)
                 const DWinOut op = B.wout[rd.winOffset + c.win];
                 const staramd_transcript tp = B.trPool[op.trOffset + c.rank];
-                overlap1 = chimBlocksOverlap(tp, B.exPool + op.exOffset + tp.exonOffset, t, x);
+                overlap1 = blocksOverlap(B.exPool + op.exOffset + tp.exonOffset, (u32)tp.nExons, x, ne);
             }
             if (chimScore > c.scoreBest) {
                 c.win = w; c.rank = k; c.have = true;

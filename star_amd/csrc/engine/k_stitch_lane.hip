@@ -5,7 +5,7 @@
 //   stitchAlignToTranscript source/stitchAlignToTranscript.cpp:9-415 (stitch_scalar.h)
 //   extendAlign             source/extendAlign.cpp:6-93             (stitch_scalar.h)
 //   binarySearch2           source/binarySearch2.cpp:3-43           (stitch_scalar.h)
-//   blocksOverlap           source/blocksOverlap.cpp:3-40
+//   blocksOverlap           source/blocksOverlap.cpp:3-40           (../chim_pair.h)
 //
 // Why a second mapping next to the wave-cooperative walk of k_stitch.hip.  The cooperative kernel gives a window to a
 // whole wavefront: its per-base loops use all 64 lanes, but the control flow between them -- the include/exclude walk, the leaf filters,
@@ -42,28 +42,13 @@ struct LaneRec { u8 *arena; u32 arenaBytes, top, nWinTr; i32 bestScore; bool ove
 
 __device__ __forceinline__ const staramd_transcript *lrecT(const LaneRec &w, u32 k) { return (const staramd_transcript *)(w.arena + (u32)w.rank[k] * 32u); }
 
-// blocksOverlap.cpp:3-40 on two exon lists
-__device__ static u32 blocksOverlapLane(const staramd_exon *e1, u32 n1, const staramd_exon *e2, u32 n2) {
-    u32 i1 = 0, i2 = 0, nOverlap = 0;
-    while (i1 < n1 && i2 < n2) {
-        const u64 rs1 = e1[i1].R, rs2 = e2[i2].R;
-        const u64 re1 = rs1 + e1[i1].L, re2 = rs2 + e2[i2].L;
-        const u64 gs1 = e1[i1].G, gs2 = e2[i2].G;
-        if (rs1 >= re2) i2++;
-        else if (rs2 >= re1) i1++;
-        else if (gs1 - rs1 != gs2 - rs2) { if (re1 >= re2) i2++; if (re2 >= re1) i1++; }
-        else { nOverlap += (u32)(min(re1, re2) - max(rs1, rs2)); if (re1 >= re2) i2++; if (re2 >= re1) i1++; }
-    }
-    return nOverlap;
-}
-
 // de-duplication against the recorded transcripts and ranked insert (stitchWindowAligns.cpp:267-303); t / ex = the candidate
 __device__ static void recordLane(const staramd_params &P, const staramd_transcript &t, const staramd_exon *ex, LaneRec &wr) {
     const int Score = t.maxScore; const u32 ne = t.nExons;
     u32 iTr = 0;
     while (iTr < wr.nWinTr) {
         const staramd_transcript *r = lrecT(wr, iTr);
-        const u32 nOverlap = blocksOverlapLane(ex, ne, (const staramd_exon *)((const u8 *)r + LREC_HDR), (u32)r->nExons);
+        const u32 nOverlap = blocksOverlap(ex, ne, (const staramd_exon *)((const u8 *)r + LREC_HDR), (u32)r->nExons);
         const u32 uNew = t.mappedLength - nOverlap, uOld = r->mappedLength - nOverlap;
         if (uNew == 0 && Score < r->maxScore) break;                                  // new one adds nothing and scores lower: dropped
         else if (uOld == 0) { for (u32 ii = iTr + 1; ii < wr.nWinTr; ii++) wr.rank[ii - 1] = wr.rank[ii]; wr.nWinTr--; }   // old one adds nothing: removed

@@ -2,6 +2,7 @@
 // restatement kept for the shadow-validation build (stitch_scalar.h).
 #pragma once
 #include "launch_geom.h"                   // Hdr, SFrame
+#include "../chim_pair.h"                  // blocksOverlap; the pair rule of chimeric detection
 
 extern __shared__ u32 ldsReads[];          // blockDim.x * ldsWords 32-bit words: 4-bit packed read of every lane
 

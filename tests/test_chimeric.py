@@ -16,7 +16,11 @@ CASES = [("pe150_chim", ["--chimSegmentMin", "15", "--chimJunctionOverhangMin", 
          ("pe101", ["--chimSegmentMin", "12", "--chimJunctionOverhangMin", "12", "--outFilterType", "BySJout"]),
          ("se50", ["--chimSegmentMin", "12", "--chimJunctionOverhangMin", "12", "--chimFilter", "None"]),
          ("pe101_sparse3", ["--chimSegmentMin", "15", "--runThreadN", "3"]),
-         ("pe76_overlap", ["--chimSegmentMin", "10", "--chimJunctionOverhangMin", "10", "--chimMainSegmentMultNmax", "1"])]
+         ("pe76_overlap", ["--chimSegmentMin", "10", "--chimJunctionOverhangMin", "10", "--chimMainSegmentMultNmax", "1"]),
+         # mate 1 shorter than the junction scans inside mate 2: the scan steps over offset readLength[0]
+         ("pe150_chim", ["--chimSegmentMin", "12", "--chimJunctionOverhangMin", "10", "--clip5pNbases", "100", "0"]),
+         # alignments with introns of both strands stay in: partners whose two motif counts are both positive
+         ("pe150_chim", ["--chimSegmentMin", "15", "--chimJunctionOverhangMin", "15", "--outFilterIntronStrands", "None", "--chimScoreDropMax", "60"])]
 
 MULT = [("pe150_chim", ["--chimSegmentMin", "15", "--chimJunctionOverhangMin", "15", "--chimMultimapNmax", "10"]),
         ("pe150_chim", ["--chimSegmentMin", "12", "--chimJunctionOverhangMin", "8", "--chimOutJunctionFormat", "1", "--chimMultimapNmax", "20", "--chimMultimapScoreRange", "3",
@@ -25,7 +29,9 @@ MULT = [("pe150_chim", ["--chimSegmentMin", "15", "--chimJunctionOverhangMin", "
         ("se50", ["--chimSegmentMin", "12", "--chimJunctionOverhangMin", "12", "--chimMultimapNmax", "5", "--chimFilter", "None", "--chimScoreDropMax", "30"]),
         ("pe101", ["--chimSegmentMin", "12", "--chimMultimapNmax", "2", "--chimMultimapScoreRange", "0", "--outFilterType", "BySJout", "--twopassMode", "Basic"]),
         ("pe76_overlap", ["--chimSegmentMin", "10", "--chimJunctionOverhangMin", "10", "--chimMultimapNmax", "50", "--chimScoreMin", "1", "--chimScoreSeparation", "1",
-                          "--chimScoreJunctionNonGTAG", "0", "--chimSegmentReadGapMax", "3", "--runThreadN", "3"])]                     # Arriba's options (without mate merging)
+                          "--chimScoreJunctionNonGTAG", "0", "--chimSegmentReadGapMax", "3", "--runThreadN", "3"]),                     # Arriba's options (without mate merging)
+        # alignments with introns of both strands stay in: for this algorithm their strand is undefined
+        ("pe150_chim", ["--chimSegmentMin", "15", "--chimJunctionOverhangMin", "15", "--chimMultimapNmax", "10", "--outFilterIntronStrands", "None", "--chimScoreDropMax", "60"])]
 
 
 @pytest.mark.parametrize("name,more", MULT)
