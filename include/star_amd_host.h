@@ -40,6 +40,22 @@ void  sah_engines_ready(void *h);
 /* --gpuBAMcompression Device: every BAM record block is compressed through fn (staramd_bgzf_compress of include/star_amd_bgzf.h, with the compressor as
  * `user`); process-wide, NULL uninstalls.  A run with Device and no fn installed fails at its first batch. */
 void  sah_set_bgzf_device_fn(int (*fn)(void *user, int level, uint32_t nSeg, const uint8_t *const *in, const uint64_t *inLen, uint8_t *out, uint64_t outCap, uint64_t *outLen), void *user);
+/* --gpuBAMsort Device: the records of Aligned.sortedByCoord.out.bam go to `sorter` as each batch is emitted (append) and come back as BGZF members at
+ * the end of the run (finish); the functions are those of include/star_amd_bamsort.h (keys: staramd_bam_key).  Process-wide, NULL uninstalls.  A run
+ * with Device and no sorter installed fails at its first batch.  When append answers 1 (the sorter's budget is used up) the run goes on the Host way:
+ * the appends so far are downloaded, the sorter is emptied (finish without a sink), one line goes to Log.out. */
+typedef struct sah_bamsort_fns {
+    int (*append)(void *sorter, const uint8_t *records, uint64_t bytes, const void *keys, uint32_t n);
+    int (*download)(void *sorter, uint32_t iAppend, uint8_t *records);
+    int (*finish)(void *sorter, int level, int (*sink)(void *user, const uint8_t *bytes, uint64_t n), void *user, uint64_t stats[8]);
+    const char *(*last_error)(void);
+} sah_bamsort_fns;
+void  sah_set_bamsort_device(const sah_bamsort_fns *fns, void *sorter);
+int   sah_bamsort_on_device(void *h);                                   /* 1: --gpuBAMsort Device */
+uint64_t sah_bamsort_budget(void *h);                                   /* --gpuBAMsortHBM: what staramd_bamsort_create is to be given */
+/* the coordinate sort of this run so far: [0] records ordered on the device, [1] their bytes (both set by the end of the run), [2] appends the device took,
+ * [3] 1 when the run spilled to the Host path */
+void  sah_bam_sort_counts(void *h, uint64_t out[4]);
 /* chimeric detection (--chimSegmentMin > 0, --chimMultimapNmax 0, no merging of overlapping mates): the engine runs the partner loop (staramd_params::resultSelect 2)
  * instead of returning every transcript of every window.  Call before the engine contexts are created, when staramd_capabilities() has STARAMD_CAP_CHIM_SELECT;
  * returns 1 when the run's parameters now say so, 0 when they do not qualify. */

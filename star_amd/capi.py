@@ -240,6 +240,7 @@ class HostRun:
         self.genome = L.sah_genome(self.h)
         self.params = L.sah_params(self.h)
         self._bgzf = None
+        self._bamsort = None
 
     def set_bgzf_device(self, bz):
         """--gpuBAMcompression Device: BAM records of this run are compressed by `bz` (a BgzfDevice; None uninstalls).  The hook is process-wide
@@ -251,6 +252,30 @@ class HostRun:
         else:
             L.sah_set_bgzf_device_fn(C.cast(bz.L.staramd_bgzf_compress, C.c_void_p), bz.z)
         self._bgzf = bz
+
+    def set_bamsort_device(self, bs):
+        """--gpuBAMsort Device: the records of this run's Aligned.sortedByCoord.out.bam go to `bs` (a BamSortDevice; None uninstalls).  Process-wide
+        (sah_set_bamsort_device); close() uninstalls it."""
+        L = self.L
+        L.sah_set_bamsort_device.restype = None; L.sah_set_bamsort_device.argtypes = [C.c_void_p, C.c_void_p]
+        if bs is None:
+            L.sah_set_bamsort_device(None, None)
+        else:
+            fns, s = bs.fns()
+            L.sah_set_bamsort_device(C.byref(fns), s)
+        self._bamsort = bs
+
+    def bamsort_budget(self):
+        """--gpuBAMsortHBM: what the run's BamSortDevice is to be created with"""
+        self.L.sah_bamsort_budget.restype = C.c_uint64; self.L.sah_bamsort_budget.argtypes = [C.c_void_p]
+        return self.L.sah_bamsort_budget(self.h)
+
+    def bam_sort_counts(self):
+        """sah_bam_sort_counts: [records ordered on the device, their bytes, appends the device took, 1 when the run spilled to the host]"""
+        self.L.sah_bam_sort_counts.restype = None; self.L.sah_bam_sort_counts.argtypes = [C.c_void_p, u64p]
+        out = (C.c_uint64 * 4)()
+        self.L.sah_bam_sort_counts(self.h, out)
+        return list(out)
 
     def next_batch(self, max_reads):
         b = Batch()
@@ -316,6 +341,8 @@ class HostRun:
             self.h = None
         if self._bgzf is not None:
             self.set_bgzf_device(None)
+        if self._bamsort is not None:
+            self.set_bamsort_device(None)
 
 
 class Engine:
@@ -450,6 +477,78 @@ class BgzfDevice:
         if self.z:
             self.L.staramd_bgzf_destroy(self.z)
             self.z = C.c_void_p()
+
+
+class BamKey(C.Structure):
+    """staramd_bam_key (include/star_amd_bamsort.h)"""
+    _fields_ = [("g", C.c_uint64), ("r", C.c_uint64), ("off", C.c_uint64), ("len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+BAMSORT_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64)
+
+
+class BamSortFns(C.Structure):
+    """sah_bamsort_fns (include/star_amd_host.h)"""
+    _fields_ = [("append", C.c_void_p), ("download", C.c_void_p), ("finish", C.c_void_p), ("last_error", C.c_void_p)]
+
+
+class BamSortDevice:
+    """include/star_amd_bamsort.h: records ordered by (g, r, order of appending) and BGZF-compressed on the MI355X (k_bamsort.hip in libstaramd.so), with
+    the stream and kernels of `bz` (a BgzfDevice, which must stay open); lib_path: another library with that ABI -- the one `bz` came from."""
+
+    def __init__(self, bz, budget=0, lib_path=None):
+        L = C.CDLL(lib_path or _need(ENGINE_PATH))
+        L.staramd_bamsort_create.restype = C.c_int
+        L.staramd_bamsort_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_uint64]
+        L.staramd_bamsort_append.restype = C.c_int
+        L.staramd_bamsort_append.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(BamKey), C.c_uint32]
+        L.staramd_bamsort_download.restype = C.c_int
+        L.staramd_bamsort_download.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.staramd_bamsort_finish.restype = C.c_int
+        L.staramd_bamsort_finish.argtypes = [C.c_void_p, C.c_int, BAMSORT_SINK, C.c_void_p, u64p]
+        L.staramd_bamsort_destroy.restype = None; L.staramd_bamsort_destroy.argtypes = [C.c_void_p]
+        L.staramd_bamsort_last_error.restype = C.c_char_p
+        self.L = L
+        self.bz = bz
+        self.s = C.c_void_p()
+        self.stats = [0] * 8
+        if L.staramd_bamsort_create(C.byref(self.s), bz.z, budget) != 0:
+            raise RuntimeError("staramd_bamsort_create failed: %s" % L.staramd_bamsort_last_error().decode())
+
+    def append(self, records, keys):
+        """records: bytes; keys: (g, r, off, len) per record, off into `records`.  True = taken, False = it does not fit the budget (nothing taken)"""
+        buf = C.create_string_buffer(bytes(records), max(len(records), 1))
+        ks = (BamKey * max(len(keys), 1))(*[BamKey(g, r, off, ln, 0) for g, r, off, ln in keys])
+        rc = self.L.staramd_bamsort_append(self.s, buf, len(records), ks, len(keys))
+        if rc < 0:
+            raise RuntimeError("staramd_bamsort_append failed: %s" % self.L.staramd_bamsort_last_error().decode())
+        return rc == 0
+
+    def download(self, i_append, n_bytes):
+        out = C.create_string_buffer(max(n_bytes, 1))
+        if self.L.staramd_bamsort_download(self.s, i_append, out) != 0:
+            raise RuntimeError("staramd_bamsort_download failed: %s" % self.L.staramd_bamsort_last_error().decode())
+        return out.raw[:n_bytes]
+
+    def finish(self, level):
+        """the BGZF members of the ordered stream, as bytes; the sorter is empty afterwards.  self.stats: the eight counters of the call"""
+        parts = []
+        sink = BAMSORT_SINK(lambda user, p, n: parts.append(C.string_at(p, n)) or 0)
+        st = (C.c_uint64 * 8)()
+        if self.L.staramd_bamsort_finish(self.s, level, sink, None, st) != 0:
+            raise RuntimeError("staramd_bamsort_finish failed: %s" % self.L.staramd_bamsort_last_error().decode())
+        self.stats = list(st)
+        return b"".join(parts)
+
+    def fns(self):
+        """(sah_bamsort_fns, sorter) for HostRun.set_bamsort_device"""
+        f = BamSortFns(*[C.cast(getattr(self.L, "staramd_bamsort_" + n), C.c_void_p) for n in ("append", "download", "finish", "last_error")])
+        return f, self.s
+
+    def close(self):
+        if self.s:
+            self.L.staramd_bamsort_destroy(self.s)
+            self.s = C.c_void_p()
 
 
 class device_sjdb_insertion:

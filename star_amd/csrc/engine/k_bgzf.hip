@@ -27,6 +27,7 @@
 #include <chrono>
 #include <algorithm>
 #include "../../../include/star_amd_bgzf.h"
+#include "bgzf_resident.h"
 
 namespace {
 
@@ -561,7 +562,32 @@ void copyPieces(const std::vector<Piece> &ps, uint64_t total) {
     run();
     for (auto &t : th) t.join();
 }
+// the three kernels of one call, on the compressor's stream: the one statement of their launch (staramd_bgzf_compress and bgzfCompressResident)
+int launchKernels(staramd_bgzf *z, const uint8_t *dIn, const uint64_t *dBlkOff, const uint32_t *dBlkLen, uint32_t nb, int level, uint8_t *dOut, uint64_t *dOff) {
+    const uint32_t grid = std::min(nb, z->grid);
+    hipLaunchKernelGGL(k_bgzf_blocks, dim3(grid), dim3(NT), 0, z->st, dIn, dBlkOff, dBlkLen, nb, level, z->dScratch, z->dSlots, z->dSizes);
+    BZ_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_bgzf_scan, dim3(1), dim3(NT), 0, z->st, z->dSizes, nb, dOff);
+    BZ_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_bgzf_compact, dim3(std::min(nb, 4096u)), dim3(NT), 0, z->st, z->dSlots, z->dSizes, dOff, nb, dOut);
+    BZ_TRY(hipGetLastError());
+    return 0;
+}
 }  // namespace
+
+// ---- input resident on the device (bgzf_resident.h) ------------------------------------------------------------------------------------------
+void bgzfResidentInfo(staramd_bgzf *z, int *device, hipStream_t *stream, uint32_t *grid) { *device = z->device; *stream = z->st; *grid = z->grid; }
+void bgzfResidentLock(staramd_bgzf *z) { z->mu.lock(); }
+void bgzfResidentUnlock(staramd_bgzf *z) { z->mu.unlock(); }
+int bgzfResidentReserve(staramd_bgzf *z, uint64_t nb) {
+    BZ_TRY(hipSetDevice(z->device));
+    return growBlk(z, nb);
+}
+int bgzfCompressResident(staramd_bgzf *z, const uint8_t *dIn, const uint64_t *dBlkOff, const uint32_t *dBlkLen, uint32_t nb, int level, uint8_t *dOut, uint64_t *dOff) {
+    if (level < -1 || level > 9) return fail("compression level " + std::to_string(level) + " is not in -1..9");
+    if (nb == 0 || nb > z->capBlk) return fail("bgzfCompressResident: " + std::to_string(nb) + " blocks, room reserved for " + std::to_string(z->capBlk));
+    return launchKernels(z, dIn, dBlkOff, dBlkLen, nb, level, dOut, dOff);
+}
 
 extern "C" {
 
@@ -632,13 +658,7 @@ int staramd_bgzf_compress(void *zv, int level, uint32_t nSeg, const uint8_t *con
     BZ_TRY(hipMemcpyAsync(z->dBlkOff, blkOff.data(), nb * 8, hipMemcpyHostToDevice, z->st));
     BZ_TRY(hipMemcpyAsync(z->dBlkLen, blkLen.data(), nb * 4, hipMemcpyHostToDevice, z->st));
     BZ_TRY(hipEventRecord(z->ev[1], z->st));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(nb, z->grid);
-    hipLaunchKernelGGL(k_bgzf_blocks, dim3(grid), dim3(NT), 0, z->st, z->dIn, z->dBlkOff, z->dBlkLen, (uint32_t)nb, level, z->dScratch, z->dSlots, z->dSizes);
-    BZ_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bgzf_scan, dim3(1), dim3(NT), 0, z->st, z->dSizes, (uint32_t)nb, z->dOff);
-    BZ_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bgzf_compact, dim3((uint32_t)std::min<uint64_t>(nb, 4096)), dim3(NT), 0, z->st, z->dSlots, z->dSizes, z->dOff, (uint32_t)nb, z->dOut);
-    BZ_TRY(hipGetLastError());
+    if (launchKernels(z, z->dIn, z->dBlkOff, z->dBlkLen, (uint32_t)nb, level, z->dOut, z->dOff)) return -1;
     BZ_TRY(hipMemcpyAsync(z->hOff, z->dOff, (nb + 1) * 8, hipMemcpyDeviceToHost, z->st));
     BZ_TRY(hipEventRecord(z->ev[2], z->st));
     BZ_TRY(hipStreamSynchronize(z->st));

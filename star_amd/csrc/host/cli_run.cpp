@@ -41,6 +41,7 @@
 #include "../../../include/star_amd_cli.h"
 #include "../../../include/star_amd_async.h"
 #include "../../../include/star_amd_bgzf.h"
+#include "../../../include/star_amd_bamsort.h"
 
 // the device BGZF compressor (k_bgzf.hip) is in the shipped engine library only: the front ends linked against the oracle / the emulated engine run
 // without it, and a run that asks for it there fails at its first batch (sah_set_bgzf_device_fn)
@@ -49,6 +50,13 @@ __attribute__((weak)) int staramd_bgzf_create(staramd_bgzf **out, int device, ui
 __attribute__((weak)) int staramd_bgzf_compress(void *z, int level, uint32_t nSeg, const uint8_t *const *in, const uint64_t *inLen, uint8_t *out, uint64_t outCap, uint64_t *outLen);
 __attribute__((weak)) void staramd_bgzf_destroy(staramd_bgzf *z);
 __attribute__((weak)) const char *staramd_bgzf_last_error(void);
+// likewise the device sorter of Aligned.sortedByCoord.out.bam (k_bamsort.hip, sah_set_bamsort_device)
+__attribute__((weak)) int staramd_bamsort_create(staramd_bamsort **out, staramd_bgzf *z, uint64_t hbmBudgetBytes);
+__attribute__((weak)) int staramd_bamsort_append(staramd_bamsort *s, const uint8_t *records, uint64_t bytes, const staramd_bam_key *keys, uint32_t n);
+__attribute__((weak)) int staramd_bamsort_download(staramd_bamsort *s, uint32_t iAppend, uint8_t *records);
+__attribute__((weak)) int staramd_bamsort_finish(staramd_bamsort *s, int level, int (*sink)(void *user, const uint8_t *bytes, uint64_t n), void *user, uint64_t stats[8]);
+__attribute__((weak)) void staramd_bamsort_destroy(staramd_bamsort *s);
+__attribute__((weak)) const char *staramd_bamsort_last_error(void);
 }
 
 namespace {
@@ -202,11 +210,13 @@ struct Engines {
     int nOwners = 0, nDev = 0;                      // contexts = mapper threads; context d belongs to owner d % nOwners
     std::vector<staramd_ctx *> ctx, owners;         // index changes go to the owners; the contexts that share an index follow
     staramd_bgzf *bgzf = nullptr;                   // --gpuBAMcompression Device: one compressor on the first device, installed as the host library's hook for the length of the run
+    staramd_bamsort *bamsort = nullptr;             // --gpuBAMsort Device: the sorter of Aligned.sortedByCoord.out.bam beside it (it works with the compressor's stream and kernels)
     explicit Engines(void *h) : h(h) {}
     ~Engines() { release(); }
     void release() {
         sah_set_sjdb_resident_fn(nullptr, nullptr);
         for (int d = (int)ctx.size() - 1; d >= 0; d--) if (ctx[d]) { staramd_destroy(ctx[d]); ctx[d] = nullptr; }      // sharers before their owners
+        if (bamsort) { sah_set_bamsort_device(nullptr, nullptr); staramd_bamsort_destroy(bamsort); bamsort = nullptr; }
         if (bgzf) { sah_set_bgzf_device_fn(nullptr, nullptr); staramd_bgzf_destroy(bgzf); bgzf = nullptr; }
     }
     // 0, or the exit code of the run
@@ -232,9 +242,19 @@ struct Engines {
         for (int d = nOwners; d < nDev; d++) if (!rcs[d % nOwners]) { rcs[d] = staramd_create_shared(&ctx[d], ctx[d % nOwners], (uint32_t)batchReads, 0); if (rcs[d]) es[d] = staramd_last_error(); }
         for (int d = 0; d < nDev; d++) if (rcs[d]) { fprintf(stderr, "\nEXITING because of FATAL ERROR: cannot initialise the MI355X engine on device %d: %s\n", devices[d % nOwners], es[d].c_str()); return 105; }
         rep.indexUploadSeconds = since(tu);
-        if (sah_bgzf_on_device(h) && staramd_bgzf_create && staramd_bgzf_compress && staramd_bgzf_destroy && staramd_bgzf_last_error) {
+        const bool sortDev = sah_bamsort_on_device(h) && staramd_bamsort_create && staramd_bamsort_append && staramd_bamsort_download && staramd_bamsort_finish && staramd_bamsort_destroy && staramd_bamsort_last_error;
+        if ((sah_bgzf_on_device(h) || sortDev) && staramd_bgzf_create && staramd_bgzf_compress && staramd_bgzf_destroy && staramd_bgzf_last_error) {
             if (staramd_bgzf_create(&bgzf, devices[0], 0)) { fprintf(stderr, "\nEXITING because of FATAL ERROR: cannot initialise the BGZF compressor on device %d: %s\n", devices[0], staramd_bgzf_last_error()); return 105; }
-            sah_set_bgzf_device_fn(staramd_bgzf_compress, bgzf);
+            if (sah_bgzf_on_device(h)) sah_set_bgzf_device_fn(staramd_bgzf_compress, bgzf);
+        }
+        if (sortDev && bgzf) {
+            if (staramd_bamsort_create(&bamsort, bgzf, sah_bamsort_budget(h))) { fprintf(stderr, "\nEXITING because of FATAL ERROR: cannot initialise the BAM sorter on device %d: %s\n", devices[0], staramd_bamsort_last_error()); return 105; }
+            static const sah_bamsort_fns fns = {
+                [](void *s, const uint8_t *rec, uint64_t bytes, const void *keys, uint32_t n) { return staramd_bamsort_append((staramd_bamsort *)s, rec, bytes, (const staramd_bam_key *)keys, n); },
+                [](void *s, uint32_t i, uint8_t *rec) { return staramd_bamsort_download((staramd_bamsort *)s, i, rec); },
+                [](void *s, int level, int (*sink)(void *, const uint8_t *, uint64_t), void *user, uint64_t *stats) { return staramd_bamsort_finish((staramd_bamsort *)s, level, sink, user, stats); },
+                staramd_bamsort_last_error};
+            sah_set_bamsort_device(&fns, bamsort);
         }
         owners.assign(ctx.begin(), ctx.begin() + nOwners);
 #ifndef STARAMD_NO_RESIDENT_SJDB

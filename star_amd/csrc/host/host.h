@@ -135,6 +135,8 @@ struct RunParams {
     bool outSAMmodeNoQS = false;
     bool outBAMunsorted = false, outBAMcoord = false; bool outSAMnone = false; int outBAMcompression = 1;   // --outSAMtype BAM Unsorted | None, --outBAMcompression
     bool gpuBAMdevice = false;           // --gpuBAMcompression Device: BAM records deflated on the MI355X through the hook of setBgzfDeviceFn
+    bool gpuBAMsortDevice = false; uint64_t gpuBAMsortHBM = 0;      // --gpuBAMsort Device: the records of Aligned.sortedByCoord.out.bam are kept, ordered and deflated on the MI355X
+                                                                    // (sah_set_bamsort_device); --gpuBAMsortHBM: the sorter's budget of device memory, 0 = its default
     std::vector<std::string> outSAMattrOrder = {"NH", "HI", "AS", "nM"};   // Standard; the parsed list, read by the checks of parse()
     // the list as codes, the list of Aligned.toTranscriptome.out.bam, and what the record writers ask of the list: decoded once, at the end of parse()
     SamAttrList outSAMattrCodes, outSAMattrCodesQuant;

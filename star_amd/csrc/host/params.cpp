@@ -281,6 +281,8 @@ std::string RunParams::parse(int argc, char **argv) {
         else if (k == "outFilterMatchNmin") { outFilterMatchNmin = (uint32_t)U(k, v); dev.outFilterMatchNmin = outFilterMatchNmin; }
         else if (k == "outFilterMatchNminOverLread") outFilterMatchNminOverLread = D(k, v);
         else if (k == "gpuBAMcompression") { const std::string &s = one(k, v); if (s == "Device") gpuBAMdevice = true; else if (s == "Host") gpuBAMdevice = false; else err = "EXITING: --gpuBAMcompression takes Host or Device"; }
+        else if (k == "gpuBAMsort") { const std::string &s = one(k, v); if (s == "Device") gpuBAMsortDevice = true; else if (s == "Host") gpuBAMsortDevice = false; else err = "EXITING: --gpuBAMsort takes Host or Device"; }
+        else if (k == "gpuBAMsortHBM") gpuBAMsortHBM = (uint64_t)U(k, v);
         else if (k == "gpuResultSelect") { const std::string &s = one(k, v); if (s == "All") dev.resultSelect = 0; else if (s == "Selected") dev.resultSelect = 1; else err = "EXITING: --gpuResultSelect takes All or Selected"; }
         else if (k == "outFilterIntronMotifs") { const std::string &s = one(k, v); if (s == "None") dev.outFilterIntronMotifs = 0; else if (s == "RemoveNoncanonical") dev.outFilterIntronMotifs = 1; else if (s == "RemoveNoncanonicalUnannotated") dev.outFilterIntronMotifs = 2; else err = "EXITING because of FATAL INPUT error: unrecognized value of --outFilterIntronMotifs=" + s; }
         else if (k == "outFilterIntronStrands") { const std::string &s = one(k, v); if (s == "RemoveInconsistentStrands") dev.outFilterIntronStrandsRemoveInconsistent = 1; else if (s == "None") dev.outFilterIntronStrandsRemoveInconsistent = 0; else err = "EXITING: unsupported --outFilterIntronStrands " + s; }
@@ -440,6 +442,8 @@ std::string RunParams::parse(int argc, char **argv) {
     if (chim.segmentMin == 0) { chim.outBam = false; chim.outJunctions = false; chim.outSamOld = false; }
     if (chim.multimapNmax > 0 && chim.outSamOld) return "EXITING because of fatal PARAMETERS error: --chimMultimapNmax > 0 (new chimeric detection) presently only works with --chimOutType Junctions/WithinBAM\nSOLUTION: re-run with --chimOutType Junctions/WithinBAM\n";
     if (wig.yes && !outBAMcoord) return "EXITING because of fatal PARAMETER error: generating signal with --outWigType requires sorted BAM\nSOLUTION: re-run STAR with with --outSAMtype BAM SortedByCoordinate, or, id you also need unsroted BAM, with --outSAMtype BAM SortedByCoordinate Unsorted\n";
+    if (gpuBAMsortDevice && !outBAMcoord) return "EXITING because of fatal PARAMETERS error: --gpuBAMsort Device orders the records of Aligned.sortedByCoord.out.bam\nSOLUTION: re-run with --outSAMtype BAM SortedByCoordinate, or without --gpuBAMsort Device\n";
+    if (gpuBAMsortDevice && wig.yes) return "EXITING because of fatal PARAMETERS error: --gpuBAMsort Device does not work with --outWigType: the signal tracks read the sorted records on the host\nSOLUTION: re-run with --gpuBAMsort Host\n";
     if (peOverlapNbasesMin > 0 && chim.segmentMin > 0) {
         if (chim.multimapNmax == 0 && (chim.outJunctions || chim.outSamOld)) return "EXITING because of fatal PARAMETERS error: --chimMultimapNmax 0 (default old chimeric detection) and --peOverlapNbasesMin > 0 (merging ovelrapping mates) presently only works with --chimOutType WithinBAM\nSOLUTION: re-run with --chimOutType WithinBAM\n";
     }

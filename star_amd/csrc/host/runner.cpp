@@ -16,6 +16,7 @@
 #include <cerrno>
 #include "../../../include/star_amd_host.h"
 #include <cstring>
+#include <cstddef>
 #include <algorithm>
 #include <ctime>
 #include <memory>
@@ -29,6 +30,13 @@
 #include <sys/mman.h>
 
 namespace staramd {
+
+// --gpuBAMsort Device: the sorter of include/star_amd_bamsort.h, installed by the driver (sah_set_bamsort_device); process-wide, like the BGZF hook
+static sah_bamsort_fns g_bamsortFns = {nullptr, nullptr, nullptr, nullptr};
+static void *g_bamsortSorter = nullptr;
+static bool bamsortInstalled() { return g_bamsortFns.append && g_bamsortFns.download && g_bamsortFns.finish && g_bamsortFns.last_error; }
+static const char *const BAMSORT_DEVICE_MISSING = "EXITING because of fatal PARAMETERS error: --gpuBAMsort Device, but no device sorter is installed (sah_set_bamsort_device)";
+static_assert(sizeof(BamKey) == 32 && offsetof(BamKey, off) == 16 && offsetof(BamKey, len) == 24, "BamKey is handed to the sorter as staramd_bam_key");
 
 // one batch with what is mapped beside it: the main batch of the one-batch-at-a-time interface (sah_next_batch ...) and every slot of the pipelined one
 // (sah_fill_slot ...) are such a set, and each batch operation has one body that takes the set
@@ -181,6 +189,9 @@ struct Runner {
     MultOrder multOrder;
     std::mt19937 rngMultOrder; std::uniform_real_distribution<double> rngUniformReal0to1{0.0, 1.0};   // ReadAlign.cpp:11-12 (one stream: iChunk 0)
     std::vector<std::string> coordChunks; std::vector<BamKey> coordKeys;     // --outSAMtype BAM SortedByCoordinate: every record, until finish()
+    // --gpuBAMsort Device: the records are in the sorter, append by append; coordChunks has an empty entry per append, so that BamKey::chunk is the append's number
+    std::vector<uint64_t> sortAppendBytes; bool sortSpilled = false; uint64_t sortCounts[2] = {0, 0}, sortAppendsTaken = 0;
+    bool sortOnDevice() const { return P.gpuBAMsortDevice && !sortSpilled; }
     int wireTable = 0;                                // which junction table sah_sj_export / import / clear address: 0 = sj, 1 = sj1
     OutSJ &wire() { if (wireTable != 1) sjBg.drainInto(sj); return wireTable == 1 ? sj1 : sj; }
     // The output junction table grows by one record per junction per read.  Whenever it passes sjKick records it is handed to a thread that collapses it and folds it
@@ -407,6 +418,7 @@ struct Runner {
         on.randomOrder = P.outMultimapperRandom;
         on.timing = hostTiming;
         if (on.devBam && !bgzfDeviceInstalled()) { error = BGZF_DEVICE_MISSING; return false; }
+        if (on.coordKeys && P.gpuBAMsortDevice && !bamsortInstalled()) { error = BAMSORT_DEVICE_MISSING; return false; }
         // T contiguous read ranges, formatted by Wk worker threads that take the next range when they are done with one: with as many
         // ranges as threads the section lasts as long as its slowest thread, and on a shared host (the GPU boxes: 16 CPUs of a 256-thread machine) one descheduled
         // thread held the batch for several times the mean (per-thread busy 2.5 - 5.6 ms in a 24 ms section).  Four ranges per thread; gene counting keeps one
@@ -497,6 +509,20 @@ struct Runner {
         error = bgzfCompressDevice(jobs, P.runThreadN);
         if (pl.on.timing) fprintf(stderr, "  emit: BAM records of %zu ranges compressed on the device, %.2f ms\n", jobs.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count());
     }
+    // --gpuBAMsort Device, the sorter's budget is used up: every append so far comes back into its entry of coordChunks, the sorter is emptied
+    bool spillSort() {
+        for (size_t i = 0; i < sortAppendBytes.size(); i++) {
+            coordChunks[i].resize(sortAppendBytes[i]);
+            if (g_bamsortFns.download(g_bamsortSorter, (uint32_t)i, (uint8_t *)&coordChunks[i][0])) { error = std::string("EXITING because of fatal ERROR: --gpuBAMsort Device: ") + g_bamsortFns.last_error(); return false; }
+        }
+        if (g_bamsortFns.finish(g_bamsortSorter, 0, nullptr, nullptr, nullptr)) { error = std::string("EXITING because of fatal ERROR: --gpuBAMsort Device: ") + g_bamsortFns.last_error(); return false; }
+        sortSpilled = true;
+        if (FILE *lo = fopen((P.outFileNamePrefix + "Log.out").c_str(), "ab")) {
+            fprintf(lo, "--gpuBAMsort Device: the records no longer fit the sorter's budget of device memory after %zu appends; they were brought back and the coordinate sort runs on the host\n", sortAppendBytes.size());
+            fclose(lo);
+        }
+        return true;
+    }
     // step 5, serial and in range order: the ranges into the run's tables and side files
     bool foldRanges(const EmitPlan &pl, std::chrono::steady_clock::time_point te2) {
         const EmitOutputs &on = pl.on;
@@ -517,7 +543,14 @@ struct Runner {
             for (uint32_t t = 0; t < T; t++) {
                 if (R[t].keys.empty()) continue;
                 uint32_t chunk = (uint32_t)coordChunks.size();
-                for (BamKey &k : R[t].keys) { k.chunk = chunk; coordKeys.push_back(k); }
+                for (BamKey &k : R[t].keys) k.chunk = chunk;
+                if (sortOnDevice()) {                                // the records into device memory, only the keys stay here
+                    const int rc = g_bamsortFns.append(g_bamsortSorter, (const uint8_t *)R[t].raw.data(), R[t].raw.size(), R[t].keys.data(), (uint32_t)R[t].keys.size());
+                    if (rc < 0) { error = std::string("EXITING because of fatal ERROR: --gpuBAMsort Device: ") + g_bamsortFns.last_error(); return false; }
+                    if (rc == 0) { coordKeys.insert(coordKeys.end(), R[t].keys.begin(), R[t].keys.end()); coordChunks.emplace_back(); sortAppendBytes.push_back(R[t].raw.size()); sortAppendsTaken++; continue; }
+                    if (!spillSort()) return false;                 // it took nothing: this range and the rest of the run go the Host way
+                }
+                coordKeys.insert(coordKeys.end(), R[t].keys.begin(), R[t].keys.end());
                 coordChunks.emplace_back(P.outBAMunsorted ? R[t].raw : std::move(R[t].raw));
             }
         if (on.stage1) {
@@ -579,6 +612,23 @@ struct Runner {
         std::string h;
         if (!bgzfCompress(post->bamHeader(true), P.outBAMcompression, h)) { if (!toStdout) fclose(f); return "EXITING because of fatal ERROR: BGZF compression failed"; }
         fwrite(h.data(), 1, h.size(), f);
+        if (sortOnDevice()) {                                       // --gpuBAMsort Device: ordered, laid out and deflated where the records are; the members come back in order
+            if (!bamsortInstalled()) { if (!toStdout) fclose(f); return BAMSORT_DEVICE_MISSING; }
+            int (*put)(void *, const uint8_t *, uint64_t) = [](void *u, const uint8_t *b, uint64_t n) -> int { return fwrite(b, 1, n, (FILE *)u) == n ? 0 : 1; };
+            uint64_t st[8] = {0};
+            const int rc = g_bamsortFns.finish(g_bamsortSorter, P.outBAMcompression, put, f, st);
+            std::string e; bgzfEof(e); fwrite(e.data(), 1, e.size(), f);
+            if (toStdout) fflush(stdout); else fclose(f);
+            const size_t appends = sortAppendBytes.size();
+            coordChunks.clear(); coordKeys.clear(); sortAppendBytes.clear();
+            if (rc) return std::string("EXITING because of fatal ERROR: --gpuBAMsort Device: ") + g_bamsortFns.last_error();
+            sortCounts[0] = st[0]; sortCounts[1] = st[1];
+            if (FILE *lo = fopen((P.outFileNamePrefix + "Log.out").c_str(), "ab")) {
+                fprintf(lo, "--gpuBAMsort Device: %llu records, %llu bytes of %zu appends ordered on the device\n", (unsigned long long)st[0], (unsigned long long)st[1], appends);
+                fclose(lo);
+            }
+            return "";
+        }
         std::vector<uint64_t> ord(coordKeys.size());
         for (uint64_t i = 0; i < ord.size(); i++) ord[i] = i;
         const std::vector<BamKey> &K = coordKeys;
@@ -698,7 +748,10 @@ struct Runner {
         if (P.quantGeneCounts) { error = geneCounts.write(P.outFileNamePrefix + "ReadsPerGene.out.tab", genes, stats); if (!error.empty()) return false; }
         return true;
     }
-    ~Runner() { writer.stop(); if (getenv("STARAMD_HOST_TIMING")) fprintf(stderr, "  host stages, whole run: writer %.3f s, emit: wait for a text buffer set %.3f s, format on threads %.3f s, serial tail %.3f s\n", writer.seconds, tEmitWaitSet, tEmitFormat, tEmitTail); if (samOut && samOut != stdout) fclose(samOut); if (quantOut == stdout) quantOut = nullptr; for (FILE *u : unmappedOut) if (u) fclose(u); if (chimOut) fclose(chimOut); if (quantOut) fclose(quantOut); }
+    ~Runner() {
+        writer.stop();
+        if (sortOnDevice() && !sortAppendBytes.empty() && bamsortInstalled()) (void)g_bamsortFns.finish(g_bamsortSorter, 0, nullptr, nullptr, nullptr);      // (a run that ended early leaves the process-wide sorter empty)
+        if (getenv("STARAMD_HOST_TIMING")) fprintf(stderr, "  host stages, whole run: writer %.3f s, emit: wait for a text buffer set %.3f s, format on threads %.3f s, serial tail %.3f s\n", writer.seconds, tEmitWaitSet, tEmitFormat, tEmitTail); if (samOut && samOut != stdout) fclose(samOut); if (quantOut == stdout) quantOut = nullptr; for (FILE *u : unmappedOut) if (u) fclose(u); if (chimOut) fclose(chimOut); if (quantOut) fclose(quantOut); }
 };
 
 } // namespace staramd
@@ -763,6 +816,13 @@ int sah_generate_finish(void *h, uint64_t nSA, uint64_t nSAbyte, uint64_t nSAiby
 int sah_tool_done(void *h) { return ((Runner *)h)->toolDone ? 1 : 0; }     // 1: the run was a tool mode (--runMode inputAlignmentsFromBAM) and is finished
 int sah_device(void *h) { return ((Runner *)h)->P.gpuDevice; }
 int sah_bgzf_on_device(void *h) { return ((Runner *)h)->P.gpuBAMdevice ? 1 : 0; }
+void sah_set_bamsort_device(const sah_bamsort_fns *fns, void *sorter) {
+    if (fns) staramd::g_bamsortFns = *fns; else staramd::g_bamsortFns = {nullptr, nullptr, nullptr, nullptr};
+    staramd::g_bamsortSorter = fns ? sorter : nullptr;
+}
+int sah_bamsort_on_device(void *h) { return ((Runner *)h)->P.gpuBAMsortDevice ? 1 : 0; }
+uint64_t sah_bamsort_budget(void *h) { return ((Runner *)h)->P.gpuBAMsortHBM; }
+void sah_bam_sort_counts(void *h, uint64_t out[4]) { Runner *r = (Runner *)h; out[0] = r->sortCounts[0]; out[1] = r->sortCounts[1]; out[2] = r->sortAppendsTaken; out[3] = r->sortSpilled ? 1 : 0; }
 double sah_genome_load_seconds(void *h) { return ((Runner *)h)->gi.loadSeconds; }
 void sah_cpu_add(int stage, uint64_t ns) { staramd::cpuAdd(stage, ns); }
 void sah_cpu_seconds(double out[8], int reset) { for (int i = 0; i < staramd::CPU_NSTAGE; i++) out[i] = (double)staramd::cpuTake(i, reset != 0) * 1e-9; }

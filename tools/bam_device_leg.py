@@ -2,7 +2,10 @@
 """bench.py's BAM leg (the `bam_output` configuration, same argv as bench.py:bam_leg, through capi.run_cli) once with --gpuBAMcompression Host and once
 with Device, on the same box.  One JSON line: M pairs/s in the timed region, BAM bytes, device bytes / host bytes, and the split of the device
 compression (STARAMD_HOST_TIMING lines of k_bgzf.hip: host staging copy, H2D, kernels, D2H, copy out; summed over the run).
-  python tools/bam_device_leg.py [--reads N ...bench.py flags] [ENV=V ...]     (GPU box)"""
+Then the SortedByCoordinate leg of --gpuBAMsort: compression Host + sort Host, compression Device + sort Host, compression Device + sort Device, alternated,
+--sort-repeats times each (default 2): M pairs/s in the timed region, finishSeconds (the end of the run: writer drained, sorted BAM written, SJ.out.tab)
+and, for the Device sort, the split of staramd_bamsort_finish (its STARAMD_HOST_TIMING line) with the gather kernel's bytes read + written per second.
+  python tools/bam_device_leg.py [--sorted-only] [--sort-repeats N] [--reads N ...bench.py flags] [ENV=V ...]     (GPU box)"""
 import json, os, re, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -43,12 +46,27 @@ def split(text):
     return dict({k.replace(" ", "_") + "_ms": round(v, 2) for k, v in tot.items()}, calls=calls)
 
 
+def sort_split(text):
+    """the line staramd_bamsort_finish prints: records, MB in and out, rounds, milliseconds per stage; gather_GB_s = (bytes read + bytes written) / gather time"""
+    m = re.search(r"bamsort device: (\d+) records, ([0-9.]+) -> ([0-9.]+) MB, (\d+) rounds: sort ([0-9.]+) ms, lengths \+ scan ([0-9.]+) ms, gather ([0-9.]+) ms, deflate ([0-9.]+) ms, D2H ([0-9.]+) ms, sink ([0-9.]+) ms", text)
+    if not m:
+        return None
+    v = [float(x) for x in m.groups()]
+    return {"records": int(v[0]), "MB_in": v[1], "MB_out": v[2], "rounds": int(v[3]), "sort_ms": v[4], "lengths_scan_ms": v[5], "gather_ms": v[6], "deflate_ms": v[7], "D2H_ms": v[8],
+            "sink_ms": v[9], "gather_GB_s": round(2 * v[1] / max(v[6], 1e-9), 1)}
+
+
 def main():
     env = [a for a in sys.argv[1:] if "=" in a and not a.startswith("-")]
     for a in env:
         k, v = a.split("=", 1)
         os.environ[k] = v
     sys.argv = [sys.argv[0]] + [a for a in sys.argv[1:] if a not in env]
+    sorted_only = "--sorted-only" in sys.argv
+    repeats = 2
+    if "--sort-repeats" in sys.argv:
+        k = sys.argv.index("--sort-repeats"); repeats = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
+    sys.argv = [a for a in sys.argv if a != "--sorted-only"]
     args = bench.parse()
     log = lambda s: print("bam_device_leg: " + s, file=sys.stderr, flush=True)
     g, ginfo = bench.build_genome(args, args.genome_mb, log)
@@ -61,7 +79,7 @@ def main():
     threads = max(4, min(64, bench.effective_cpus()))
     os.environ["STARAMD_HOST_TIMING"] = "1"
     out = {"reads_per_batch": args.reads, "genome_mb": args.genome_mb, "host_threads": threads}
-    for name, typ in (("unsorted", ["BAM", "Unsorted"]), ("sorted_by_coordinate", ["BAM", "SortedByCoordinate"])):
+    for name, typ in (() if sorted_only else (("unsorted", ["BAM", "Unsorted"]), ("sorted_by_coordinate", ["BAM", "SortedByCoordinate"]))):
         row = {}
         for mode in ("Host", "Device"):
             prefix = os.path.join(rd, "bam_%s_%s_" % (name, mode))
@@ -80,6 +98,25 @@ def main():
         if row["Host"]["bam_bytes"] and row["Device"]["bam_bytes"]:
             row["device_bytes_over_host_bytes"] = round(row["Device"]["bam_bytes"] / row["Host"]["bam_bytes"], 4)
         out[name] = row
+    # --gpuBAMsort: the three forms of the SortedByCoordinate run, alternated
+    forms = (("host_host", "Host", "Host"), ("device_compression", "Device", "Host"), ("device_compression_and_sort", "Device", "Device"))
+    leg = {tag: [] for tag, _, _ in forms}
+    for rep_i in range(repeats):
+        for tag, comp, srt in forms:
+            prefix = os.path.join(rd, "bamsort_%s_" % tag)
+            argv = ["--runMode", "alignReads", "--genomeDir", idx, "--readFilesIn"] + fq + ["--outFileNamePrefix", prefix, "--runThreadN", str(threads), "--gpuBatchReads",
+                    str(args.reads), "--benchWarmupReads", str(w * args.reads), "--readMapNumber", str((nb + w) * args.reads), "--outSAMtype", "BAM", "SortedByCoordinate",
+                    "--gpuBAMcompression", comp, "--gpuBAMsort", srt]
+            rc, rep, wall, text = run_captured(argv)
+            f = prefix + "Aligned.sortedByCoord.out.bam"
+            r = {"exit_code": rc, "Mpairs_s_timed_region": round(int(rep.timedReads) / max(float(rep.timedWall), 1e-9) / 1e6, 4), "finishSeconds": round(float(rep.finishSeconds), 4),
+                 "whole_run_s": round(wall, 3), "bam_bytes": os.path.getsize(f) if os.path.isfile(f) else None}
+            if srt == "Device":
+                r["finish_split"] = sort_split(text)
+            leg[tag].append(r)
+            if os.path.isfile(f):
+                os.remove(f)
+    out["sorted_by_coordinate_sort_leg"] = leg
     print(json.dumps(out))
 
 
