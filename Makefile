@@ -25,9 +25,9 @@ endef
 HOST_SRC := $(wildcard star_amd/csrc/host/*.cpp)
 HOST_LIB_SRC := $(filter-out star_amd/csrc/host/main.cpp star_amd/csrc/host/cli_run.cpp,$(HOST_SRC))
 CLI_SRC := star_amd/csrc/host/main.cpp star_amd/csrc/host/cli_run.cpp
-CLI_HDR := include/star_amd_host.h include/star_amd_index.h include/star_amd_cli.h include/star_amd.h include/star_amd_bamsort.h
+CLI_HDR := include/star_amd_host.h include/star_amd_index.h include/star_amd_cli.h include/star_amd.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_bgzf.h
 HIP_SRC  := $(wildcard star_amd/csrc/engine/*.hip) $(wildcard star_amd/csrc/index/*.hip)
-HIP_HDR  := $(wildcard star_amd/csrc/engine/*.h) $(wildcard star_amd/csrc/index/*.h) star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_index.h include/star_amd_bamsort.h
+HIP_HDR  := $(wildcard star_amd/csrc/engine/*.h) $(wildcard star_amd/csrc/index/*.h) star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_index.h include/star_amd_bamsort.h include/star_amd_signal.h
 
 all: host engine shadow cli oracle
 
@@ -36,7 +36,7 @@ engine: star_amd/lib/libstaramd.so
 cli: star_amd/bin/star_amd star_amd/lib/libstaramd_cli.so
 oracle: oracle/_build/liboracle.so oracle/_build/libindex_emul.so oracle/_build/star_amd_oracle_cli oracle/_build/libstaramd_cli_oracle.so oracle/_build/libstaramd_cli_replay.so oracle/_build/libstaramd_emul.so oracle/_build/star_amd_emul_cli
 
-star_amd/lib/libstaramd_host.so: $(HOST_LIB_SRC) star_amd/csrc/host/host.h star_amd/csrc/chim_pair.h include/star_amd.h
+star_amd/lib/libstaramd_host.so: $(HOST_LIB_SRC) star_amd/csrc/host/host.h star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_host.h include/star_amd_signal.h
 	@mkdir -p star_amd/lib
 	$(CXX) $(CXXFLAGS) -shared $(HOST_LIB_SRC) -o $@ -lz
 

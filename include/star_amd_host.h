@@ -56,6 +56,25 @@ uint64_t sah_bamsort_budget(void *h);                                   /* --gpu
 /* the coordinate sort of this run so far: [0] records ordered on the device, [1] their bytes (both set by the end of the run), [2] appends the device took,
  * [3] 1 when the run spilled to the Host path */
 void  sah_bam_sort_counts(void *h, uint64_t out[4]);
+/* --gpuSignal Device: the tracks of --outWigType are computed by the functions of include/star_amd_signal.h (params: staramd_signal_params, result:
+ * staramd_signal_result) and written by the host from the runs they return.  finish_signal takes the place of sah_bamsort_fns::finish at the end of a run
+ * with --gpuBAMsort Device (`sorter` is the one of sah_set_bamsort_device); host_records serves --runMode inputAlignmentsFromBAM, which runs inside
+ * sah_create: install before it.  Process-wide, NULL uninstalls.  A run with Device and nothing installed fails when it comes to the tracks.  A run that
+ * spilled to the Host sorter has its records on the host and takes the host's signal code (one line in Log.out says so). */
+typedef struct sah_signal_fns {
+    int (*host_records)(int device, const void *params, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, void *result);
+    int (*finish_signal)(void *sorter, int level, int (*sink)(void *user, const uint8_t *bytes, uint64_t n), void *user, uint64_t stats[8], const void *params, void *result);
+    void (*free_result)(void *result);
+    const char *(*last_error)(void);
+} sah_signal_fns;
+void  sah_set_signal_device(const sah_signal_fns *fns);
+int   sah_signal_on_device(void *h);                                    /* 1: --gpuSignal Device */
+/* the signal stage of this run: [0] 1 when the device computed the tracks, [1] records, [2] (tile, span) pairs, [3] bytes of the runs, [4] nanoseconds of the
+ * stage on the host's clock (device work or writeSignal's loop, and the writing of the files), [5..7] nanoseconds of the device's record pass, sort, tile passes */
+void  sah_signal_counts(void *h, uint64_t out[8]);
+/* the host's half of --gpuSignal Device alone (tests): the Signal.* files of the --outWig* flags and --outFileNamePrefix in argv (a command line that
+ * sah_create accepts, e.g. the tool mode's) from a staramd_signal_result.  0, or -1 with the text in errbuf */
+int   sah_signal_files_from_runs(int argc, char **argv, int nChr, const char *const *chrName, const uint64_t *chrLength, const void *result, char *errbuf, int errlen);
 /* chimeric detection (--chimSegmentMin > 0, --chimMultimapNmax 0, no merging of overlapping mates): the engine runs the partner loop (staramd_params::resultSelect 2)
  * instead of returning every transcript of every window.  Call before the engine contexts are created, when staramd_capabilities() has STARAMD_CAP_CHIM_SELECT;
  * returns 1 when the run's parameters now say so, 0 when they do not qualify. */

@@ -241,6 +241,7 @@ class HostRun:
         self.params = L.sah_params(self.h)
         self._bgzf = None
         self._bamsort = None
+        self._signal = None
 
     def set_bgzf_device(self, bz):
         """--gpuBAMcompression Device: BAM records of this run are compressed by `bz` (a BgzfDevice; None uninstalls).  The hook is process-wide
@@ -264,6 +265,27 @@ class HostRun:
             fns, s = bs.fns()
             L.sah_set_bamsort_device(C.byref(fns), s)
         self._bamsort = bs
+
+    def set_signal_device(self, sg):
+        """--gpuSignal Device: the tracks of --outWigType come from `sg` (a SignalDevice; None uninstalls).  Process-wide (sah_set_signal_device); close()
+        uninstalls it.  The tool mode (--runMode inputAlignmentsFromBAM) runs inside HostRun(): use SignalDevice.install() before it."""
+        if sg is None:
+            SignalDevice.uninstall()
+        else:
+            sg.install()
+        self._signal = sg
+
+    def signal_on_device(self):
+        """True: --gpuSignal Device"""
+        self.L.sah_signal_on_device.restype = C.c_int; self.L.sah_signal_on_device.argtypes = [C.c_void_p]
+        return bool(self.L.sah_signal_on_device(self.h))
+
+    def signal_counts(self):
+        """sah_signal_counts: [1 when the device computed the tracks, records, spans, bytes of the runs, ns of the stage, ns of the device's record pass, sort, tile passes]"""
+        self.L.sah_signal_counts.restype = None; self.L.sah_signal_counts.argtypes = [C.c_void_p, u64p]
+        out = (C.c_uint64 * 8)()
+        self.L.sah_signal_counts(self.h, out)
+        return list(out)
 
     def bamsort_budget(self):
         """--gpuBAMsortHBM: what the run's BamSortDevice is to be created with"""
@@ -343,6 +365,8 @@ class HostRun:
             self.set_bgzf_device(None)
         if self._bamsort is not None:
             self.set_bamsort_device(None)
+        if self._signal is not None:
+            self.set_signal_device(None)
 
 
 class Engine:
@@ -549,6 +573,117 @@ class BamSortDevice:
         if self.s:
             self.L.staramd_bamsort_destroy(self.s)
             self.s = C.c_void_p()
+
+
+class SignalParams(C.Structure):
+    """staramd_signal_params (include/star_amd_signal.h)"""
+    _fields_ = [("type", C.c_int32), ("strand", C.c_int32), ("nChr", C.c_uint32), ("wantNorm", C.c_uint32), ("chrLength", C.POINTER(C.c_uint32)), ("wanted", C.POINTER(C.c_uint8))]
+
+
+class SignalRun(C.Structure):
+    """staramd_signal_run"""
+    _fields_ = [("tid", C.c_int32), ("track", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("value", C.c_double)]
+
+
+class SignalResult(C.Structure):
+    """staramd_signal_result"""
+    _fields_ = [("runs", C.POINTER(SignalRun)), ("nRuns", C.c_uint64), ("norm", C.POINTER(C.c_uint32)), ("nRecords", C.c_uint64),
+                ("chrHas", C.POINTER(C.c_uint8)), ("nChr", C.c_uint32), ("pastEnd", C.c_uint32), ("stats", C.c_uint64 * 8)]
+
+
+class SignalFns(C.Structure):
+    """sah_signal_fns (include/star_amd_host.h)"""
+    _fields_ = [("host_records", C.c_void_p), ("finish_signal", C.c_void_p), ("free_result", C.c_void_p), ("last_error", C.c_void_p)]
+
+
+class SignalDevice:
+    """include/star_amd_signal.h: the tracks of --outWigType from BAM records in coordinate order on the MI355X (k_signal.hip in libstaramd.so); lib_path:
+    another library with that ABI (the wave emulator's build in the CPU tests; for sorter_tracks the one the BamSortDevice came from)."""
+
+    def __init__(self, lib_path=None):
+        L = C.CDLL(lib_path or _need(ENGINE_PATH))
+        L.staramd_signal_host_records.restype = C.c_int
+        L.staramd_signal_host_records.argtypes = [C.c_int, C.POINTER(SignalParams), C.c_void_p, C.c_uint64, u64p, C.c_uint64, C.POINTER(SignalResult)]
+        L.staramd_bamsort_finish_signal.restype = C.c_int
+        L.staramd_bamsort_finish_signal.argtypes = [C.c_void_p, C.c_int, BAMSORT_SINK, C.c_void_p, u64p, C.POINTER(SignalParams), C.POINTER(SignalResult)]
+        L.staramd_signal_free.restype = None; L.staramd_signal_free.argtypes = [C.POINTER(SignalResult)]
+        L.staramd_signal_constant.restype = C.c_uint32; L.staramd_signal_constant.argtypes = [C.c_int]
+        L.staramd_signal_last_error.restype = C.c_char_p
+        self.L = L
+        self.tile = L.staramd_signal_constant(0)
+        self.chunk = L.staramd_signal_constant(1)
+
+    @staticmethod
+    def _params(type_, strand, chr_length, wanted, want_norm):
+        n = len(chr_length)
+        ln = (C.c_uint32 * max(n, 1))(*chr_length)
+        wt = (C.c_uint8 * max(n, 1))(*[1 if w else 0 for w in wanted])
+        return SignalParams(type_, 1 if strand else 0, n, 1 if want_norm else 0, ln, wt), (ln, wt)
+
+    def _take(self, res):
+        """(runs [(tid, track, start, end, value)], norm list or None, chrHas list, pastEnd, stats) of a result, which is freed"""
+        try:
+            runs = [(r.tid, r.track, r.start, r.end, r.value) for r in (res.runs[i] for i in range(res.nRuns))]
+            norm = [res.norm[i] for i in range(res.nRecords)] if res.norm else None
+            return runs, norm, [res.chrHas[i] for i in range(res.nChr)], bool(res.pastEnd), list(res.stats)
+        finally:
+            self.L.staramd_signal_free(C.byref(res))
+
+    def host_records(self, records, type_=0, strand=True, chr_length=(), wanted=None, want_norm=True, device=0):
+        """records: list of BAM records (bytes, each with its block_size word) in coordinate order"""
+        blob = b"".join(records)
+        offs, o = [], 0
+        for r in records:
+            offs.append(o); o += len(r)
+        p, keep = self._params(type_, strand, chr_length, wanted if wanted is not None else [1] * len(chr_length), want_norm)
+        res = SignalResult()
+        buf = C.create_string_buffer(blob, max(len(blob), 1))
+        if self.L.staramd_signal_host_records(device, C.byref(p), buf, len(blob), (C.c_uint64 * max(len(offs), 1))(*offs), len(offs), C.byref(res)) != 0:
+            raise RuntimeError("staramd_signal_host_records failed: %s" % self.L.staramd_signal_last_error().decode())
+        return self._take(res)
+
+    def sorter_tracks(self, bs, level, type_=0, strand=True, chr_length=(), wanted=None, want_norm=True):
+        """staramd_bamsort_finish_signal on the BamSortDevice `bs`: (the BGZF members as bytes, the result as host_records returns it)"""
+        parts = []
+        sink = BAMSORT_SINK(lambda user, p, n: parts.append(C.string_at(p, n)) or 0)
+        st = (C.c_uint64 * 8)()
+        p, keep = self._params(type_, strand, chr_length, wanted if wanted is not None else [1] * len(chr_length), want_norm)
+        res = SignalResult()
+        if self.L.staramd_bamsort_finish_signal(bs.s, level, sink, None, st, C.byref(p), C.byref(res)) != 0:
+            raise RuntimeError("staramd_bamsort_finish_signal failed: %s" % self.L.staramd_signal_last_error().decode())
+        bs.stats = list(st)
+        return b"".join(parts), self._take(res)
+
+    def install(self):
+        """sah_set_signal_device with this library's functions (process-wide)"""
+        L = host_lib()
+        L.sah_set_signal_device.restype = None; L.sah_set_signal_device.argtypes = [C.c_void_p]
+        names = ("staramd_signal_host_records", "staramd_bamsort_finish_signal", "staramd_signal_free", "staramd_signal_last_error")
+        self._fns = SignalFns(*[C.cast(getattr(self.L, n), C.c_void_p) for n in names])
+        L.sah_set_signal_device(C.byref(self._fns))
+
+    @staticmethod
+    def uninstall():
+        L = host_lib()
+        L.sah_set_signal_device.restype = None; L.sah_set_signal_device.argtypes = [C.c_void_p]
+        L.sah_set_signal_device(None)
+
+
+def signal_files_from_runs(argv, chr_names, chr_length, runs, norm, chr_has, past_end=False):
+    """the host formatter alone (signalFromRuns of signal.cpp): the Signal.* files of a run with the --outWig* flags in `argv` (and --outFileNamePrefix)
+    from runs [(tid, track, start, end, value)], the per-record normalisation words and the has-records flags; returns the error text ("" = none)"""
+    L = host_lib()
+    L.sah_signal_files_from_runs.restype = C.c_int
+    L.sah_signal_files_from_runs.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.c_int, C.POINTER(C.c_char_p), u64p, C.POINTER(SignalResult), C.c_char_p, C.c_int]
+    args = [b"star_amd"] + [a.encode() for a in argv]
+    names = [n.encode() for n in chr_names]
+    rs = (SignalRun * max(len(runs), 1))(*[SignalRun(*r) for r in runs])
+    nm = (C.c_uint32 * max(len(norm or []), 1))(*(norm or []))
+    ch = (C.c_uint8 * max(len(chr_has), 1))(*chr_has)
+    res = SignalResult(rs, len(runs), nm if norm is not None else None, len(norm or []), ch, len(chr_has), 1 if past_end else 0)
+    err = C.create_string_buffer(4096)
+    L.sah_signal_files_from_runs(len(args), (C.c_char_p * len(args))(*args), len(names), (C.c_char_p * max(len(names), 1))(*names), (C.c_uint64 * max(len(names), 1))(*chr_length), C.byref(res), err, 4096)
+    return err.value.decode()
 
 
 class device_sjdb_insertion:

@@ -30,6 +30,7 @@
 #include <atomic>
 #include "../../../include/star_amd_bamsort.h"
 #include "bgzf_resident.h"
+#include "bamsort_resident.h"
 
 namespace {
 
@@ -143,6 +144,7 @@ struct staramd_bamsort {
     std::vector<uint64_t> g, r, addr; std::vector<uint32_t> len; uint64_t bytes = 0;      // one entry per record, in the order of appending; bytes: the sum of len = the stream's length
     uint8_t *stage[2] = {nullptr, nullptr}; uint64_t stageCap[2] = {0, 0}; hipEvent_t stageDone[2] = {}; bool stageBusy[2] = {false, false}; uint32_t nextStage = 0;
     hipEvent_t ev[12] = {};
+    BamsortAfterOrder afterOrder = nullptr; void *afterOrderUser = nullptr;              // bamsort_resident.h
 };
 
 namespace {
@@ -234,6 +236,7 @@ int finishOnDevice(staramd_bamsort *s, int level, int (*sink)(void *, const uint
         BS_TRY(rocprim::exclusive_scan(tmp, need, dLen64, dLen64, (uint64_t)0, (size_t)n64 + 1, rocprim::plus<uint64_t>(), st)); }
     const uint64_t *dDst = dLen64;
     BS_TRY(hipEventRecord(s->ev[2], st));
+    if (s->afterOrder && s->afterOrder(s->afterOrderUser, st, s->cus, dSrc, dDst, n64)) return fail("the pass over the ordered records reported an error");
     // ---- rounds
     const uint64_t total = s->bytes, nbAll = (total + IN_MAX - 1) / IN_MAX, RB = std::min(s->roundBlocks, nbAll), rounds = (nbAll + RB - 1) / RB;
     const uint64_t roundCap = RB * IN_MAX, outCap = staramd_bgzf_bound(roundCap);
@@ -398,7 +401,10 @@ int staramd_bamsort_finish(staramd_bamsort *s, int level, int (*sink)(void *user
         }
     }
     freeSlabs(s);
+    s->afterOrder = nullptr; s->afterOrderUser = nullptr;
     return rc;
 }
 
 }  // extern "C"
+
+void bamsortSetAfterOrder(staramd_bamsort *s, BamsortAfterOrder fn, void *user) { s->afterOrder = fn; s->afterOrderUser = user; }

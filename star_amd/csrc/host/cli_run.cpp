@@ -42,6 +42,7 @@
 #include "../../../include/star_amd_async.h"
 #include "../../../include/star_amd_bgzf.h"
 #include "../../../include/star_amd_bamsort.h"
+#include "../../../include/star_amd_signal.h"
 
 // the device BGZF compressor (k_bgzf.hip) is in the shipped engine library only: the front ends linked against the oracle / the emulated engine run
 // without it, and a run that asks for it there fails at its first batch (sah_set_bgzf_device_fn)
@@ -57,6 +58,11 @@ __attribute__((weak)) int staramd_bamsort_download(staramd_bamsort *s, uint32_t 
 __attribute__((weak)) int staramd_bamsort_finish(staramd_bamsort *s, int level, int (*sink)(void *user, const uint8_t *bytes, uint64_t n), void *user, uint64_t stats[8]);
 __attribute__((weak)) void staramd_bamsort_destroy(staramd_bamsort *s);
 __attribute__((weak)) const char *staramd_bamsort_last_error(void);
+// and the signal tracks on the device (k_signal.hip, sah_set_signal_device)
+__attribute__((weak)) int staramd_signal_host_records(int device, const staramd_signal_params *p, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, staramd_signal_result *out);
+__attribute__((weak)) int staramd_bamsort_finish_signal(staramd_bamsort *s, int level, int (*sink)(void *user, const uint8_t *bytes, uint64_t n), void *user, uint64_t stats[8], const staramd_signal_params *p, staramd_signal_result *out);
+__attribute__((weak)) void staramd_signal_free(staramd_signal_result *r);
+__attribute__((weak)) const char *staramd_signal_last_error(void);
 }
 
 namespace {
@@ -527,6 +533,14 @@ int staramd_cli_main(int argc, char **argv, const staramd_cli_hooks *hooks, star
     for (int i = 1; i < argc; i++) if (std::string(argv[i]) == "--version") { printf("2.7.11b\n"); return 0; }      // the version whose behaviour is reproduced (Parameters.cpp:340-343)
     CliFlags flags = splitFlags(argc, argv);
     if (!getenv("STARAMD_SJDB_HOST")) sah_set_sjdb_device_fn(staramd_sjdb_insert, flags.devices.empty() ? 0 : flags.devices[0]);   // junction insertion on the device
+    if (staramd_signal_host_records && staramd_bamsort_finish_signal && staramd_signal_free && staramd_signal_last_error) {      // --gpuSignal Device; before sah_create, where the tool mode runs
+        static const sah_signal_fns fns = {
+            [](int device, const void *p, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, void *res) { return staramd_signal_host_records(device, (const staramd_signal_params *)p, bytes, nBytes, offsets, n, (staramd_signal_result *)res); },
+            [](void *s, int level, int (*sink)(void *, const uint8_t *, uint64_t), void *user, uint64_t *stats, const void *p, void *res) { return staramd_bamsort_finish_signal((staramd_bamsort *)s, level, sink, user, stats, (const staramd_signal_params *)p, (staramd_signal_result *)res); },
+            [](void *res) { staramd_signal_free((staramd_signal_result *)res); },
+            staramd_signal_last_error};
+        sah_set_signal_device(&fns);
+    }
     LoadLock loadLock;
     loadLock.take();
     sah_set_batch_alloc(staramd_pinned_alloc, staramd_pinned_free);      // batch arrays in page-locked memory: the uploads are DMA transfers

@@ -20,6 +20,7 @@
 #include <thread>
 #include "../../../include/star_amd.h"
 #include "../../../include/star_amd_index.h"
+struct sah_signal_fns;                  // include/star_amd_host.h
 
 namespace staramd {
 // CPU seconds per pipeline stage (thread CPU clocks: what a stage COSTS, beside the wall-clock busy times that say how long it TAKES): every thread of the front end
@@ -158,6 +159,7 @@ struct RunParams {
     bool sjdbInsertYes() const { return twopass || sjdbInsertPass1(); }
     bool outFilterBySJout = false;       // --outFilterType BySJout
     ChimParams chim;                     // --chim* (chimeric.cpp)
+    bool gpuSignalDevice = false;        // --gpuSignal Device: the tracks of --outWigType are computed on the MI355X where the sorted records lie (sah_set_signal_device)
     WigParams wig;                       // --outWig* (signal.cpp)
     std::vector<std::string> outSAMattrRG, outSAMattrRGlineSplit;   // --outSAMattrRGline (Parameters_readFilesInit.cpp:64-93)
     bool outReadsUnmappedFastx = false;  // --outReadsUnmapped Fastx
@@ -453,6 +455,17 @@ int chimAlignScore(const staramd_params &D, const GenomeIndex &gi, const uint8_t
 
 // signal.cpp: coverage tracks from BAM records in coordinate order; error text or ""
 std::string writeSignal(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength, const std::string &sigFileName, const std::vector<const char *> &recs);
+// the same files from the runs of include/star_amd_signal.h (--gpuSignal Device): res is a staramd_signal_result
+std::string signalFromRuns(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength, const std::string &sigFileName, const void *res);
+// the functions behind --gpuSignal Device (sah_set_signal_device; nullptr while none is installed) and the parameters they take: a staramd_signal_params in
+// `abi`, whose arrays are this object's
+void setSignalDeviceFns(const ::sah_signal_fns *fns);
+const ::sah_signal_fns *signalDeviceFns();
+inline constexpr const char *SIGNAL_DEVICE_MISSING = "EXITING because of fatal PARAMETERS error: --gpuSignal Device, but no device signal functions are installed (sah_set_signal_device)";
+struct SignalDeviceParams {
+    std::vector<uint32_t> len; std::vector<uint8_t> wanted; alignas(8) unsigned char abi[48];
+    void set(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength);
+};
 std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, const std::string &sigFileName);   // --runMode inputAlignmentsFromBAM
 
 // ---- post-map: multMapSelect, mappedFilter, outputAlignments ----

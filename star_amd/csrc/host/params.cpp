@@ -283,6 +283,7 @@ std::string RunParams::parse(int argc, char **argv) {
         else if (k == "gpuBAMcompression") { const std::string &s = one(k, v); if (s == "Device") gpuBAMdevice = true; else if (s == "Host") gpuBAMdevice = false; else err = "EXITING: --gpuBAMcompression takes Host or Device"; }
         else if (k == "gpuBAMsort") { const std::string &s = one(k, v); if (s == "Device") gpuBAMsortDevice = true; else if (s == "Host") gpuBAMsortDevice = false; else err = "EXITING: --gpuBAMsort takes Host or Device"; }
         else if (k == "gpuBAMsortHBM") gpuBAMsortHBM = (uint64_t)U(k, v);
+        else if (k == "gpuSignal") { const std::string &s = one(k, v); if (s == "Device") gpuSignalDevice = true; else if (s == "Host") gpuSignalDevice = false; else err = "EXITING: --gpuSignal takes Host or Device"; }
         else if (k == "gpuResultSelect") { const std::string &s = one(k, v); if (s == "All") dev.resultSelect = 0; else if (s == "Selected") dev.resultSelect = 1; else err = "EXITING: --gpuResultSelect takes All or Selected"; }
         else if (k == "outFilterIntronMotifs") { const std::string &s = one(k, v); if (s == "None") dev.outFilterIntronMotifs = 0; else if (s == "RemoveNoncanonical") dev.outFilterIntronMotifs = 1; else if (s == "RemoveNoncanonicalUnannotated") dev.outFilterIntronMotifs = 2; else err = "EXITING because of FATAL INPUT error: unrecognized value of --outFilterIntronMotifs=" + s; }
         else if (k == "outFilterIntronStrands") { const std::string &s = one(k, v); if (s == "RemoveInconsistentStrands") dev.outFilterIntronStrandsRemoveInconsistent = 1; else if (s == "None") dev.outFilterIntronStrandsRemoveInconsistent = 0; else err = "EXITING: unsupported --outFilterIntronStrands " + s; }
@@ -367,7 +368,7 @@ std::string RunParams::parse(int argc, char **argv) {
     if (runModeFromBAM) {                    // Parameters.cpp:585-605
         if (!wig.yes) return "EXITING because of fatal INPUT error: at the moment --runMode inputFromBAM only works with --outWigType bedGraph OR --bamRemoveDuplicatesType Identical\nSOLUTION: re-run STAR with --outWigType bedGraph (duplicate removal is not implemented here)\n";
         if (inputBAMfile.empty()) return "EXITING because of fatal INPUT error: --runMode inputAlignmentsFromBAM needs --inputBAMfile";
-        return "";
+        return "";                                                  // (--gpuSignal Device: wig.yes holds already)
     }
     if (!readFilesManifest.empty()) {        // Parameters_readFilesInit.cpp:100-139: Read1 <tab> Read2 (or -) <tab> read group line
         std::ifstream rfM(readFilesManifest.c_str());
@@ -443,7 +444,9 @@ std::string RunParams::parse(int argc, char **argv) {
     if (chim.multimapNmax > 0 && chim.outSamOld) return "EXITING because of fatal PARAMETERS error: --chimMultimapNmax > 0 (new chimeric detection) presently only works with --chimOutType Junctions/WithinBAM\nSOLUTION: re-run with --chimOutType Junctions/WithinBAM\n";
     if (wig.yes && !outBAMcoord) return "EXITING because of fatal PARAMETER error: generating signal with --outWigType requires sorted BAM\nSOLUTION: re-run STAR with with --outSAMtype BAM SortedByCoordinate, or, id you also need unsroted BAM, with --outSAMtype BAM SortedByCoordinate Unsorted\n";
     if (gpuBAMsortDevice && !outBAMcoord) return "EXITING because of fatal PARAMETERS error: --gpuBAMsort Device orders the records of Aligned.sortedByCoord.out.bam\nSOLUTION: re-run with --outSAMtype BAM SortedByCoordinate, or without --gpuBAMsort Device\n";
-    if (gpuBAMsortDevice && wig.yes) return "EXITING because of fatal PARAMETERS error: --gpuBAMsort Device does not work with --outWigType: the signal tracks read the sorted records on the host\nSOLUTION: re-run with --gpuBAMsort Host\n";
+    if (gpuSignalDevice && !wig.yes) return "EXITING because of fatal PARAMETERS error: --gpuSignal Device computes the signal tracks of --outWigType\nSOLUTION: re-run with --outWigType bedGraph or wiggle, or without --gpuSignal Device\n";
+    if (gpuSignalDevice && !gpuBAMsortDevice) return "EXITING because of fatal PARAMETERS error: --gpuSignal Device reads the sorted records where --gpuBAMsort Device keeps them\nSOLUTION: re-run with --gpuBAMsort Device, or without --gpuSignal Device\n";
+    if (gpuBAMsortDevice && wig.yes && !gpuSignalDevice) return "EXITING because of fatal PARAMETERS error: --gpuBAMsort Device does not work with --outWigType: the signal tracks read the sorted records on the host\nSOLUTION: re-run with --gpuBAMsort Host\n";
     if (peOverlapNbasesMin > 0 && chim.segmentMin > 0) {
         if (chim.multimapNmax == 0 && (chim.outJunctions || chim.outSamOld)) return "EXITING because of fatal PARAMETERS error: --chimMultimapNmax 0 (default old chimeric detection) and --peOverlapNbasesMin > 0 (merging ovelrapping mates) presently only works with --chimOutType WithinBAM\nSOLUTION: re-run with --chimOutType WithinBAM\n";
     }

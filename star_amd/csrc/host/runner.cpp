@@ -15,6 +15,7 @@
 #include <sys/stat.h>
 #include <cerrno>
 #include "../../../include/star_amd_host.h"
+#include "../../../include/star_amd_signal.h"
 #include <cstring>
 #include <cstddef>
 #include <algorithm>
@@ -192,6 +193,7 @@ struct Runner {
     // --gpuBAMsort Device: the records are in the sorter, append by append; coordChunks has an empty entry per append, so that BamKey::chunk is the append's number
     std::vector<uint64_t> sortAppendBytes; bool sortSpilled = false; uint64_t sortCounts[2] = {0, 0}, sortAppendsTaken = 0;
     bool sortOnDevice() const { return P.gpuBAMsortDevice && !sortSpilled; }
+    uint64_t signalCounts[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // sah_signal_counts
     int wireTable = 0;                                // which junction table sah_sj_export / import / clear address: 0 = sj, 1 = sj1
     OutSJ &wire() { if (wireTable != 1) sjBg.drainInto(sj); return wireTable == 1 ? sj1 : sj; }
     // The output junction table grows by one record per junction per read.  Whenever it passes sjKick records it is handed to a thread that collapses it and folds it
@@ -616,18 +618,37 @@ struct Runner {
             if (!bamsortInstalled()) { if (!toStdout) fclose(f); return BAMSORT_DEVICE_MISSING; }
             int (*put)(void *, const uint8_t *, uint64_t) = [](void *u, const uint8_t *b, uint64_t n) -> int { return fwrite(b, 1, n, (FILE *)u) == n ? 0 : 1; };
             uint64_t st[8] = {0};
-            const int rc = g_bamsortFns.finish(g_bamsortSorter, P.outBAMcompression, put, f, st);
+            // --gpuSignal Device: the same finish, which also computes the tracks where the records lie, after the order is known; they are written once the BAM is
+            const sah_signal_fns *sig = P.wig.yes && P.gpuSignalDevice ? signalDeviceFns() : nullptr;
+            if (P.wig.yes && P.gpuSignalDevice && !sig) { if (!toStdout) fclose(f); return SIGNAL_DEVICE_MISSING; }
+            const std::vector<std::string> chrName(gi.chrName.begin(), gi.chrName.begin() + gi.view.nChrReal);
+            const std::vector<uint64_t> chrLength(gi.chrLength.begin(), gi.chrLength.begin() + gi.view.nChrReal);
+            SignalDeviceParams sp; staramd_signal_result sres; memset(&sres, 0, sizeof(sres));
+            if (sig) sp.set(P, chrName, chrLength);
+            const int rc = sig ? sig->finish_signal(g_bamsortSorter, P.outBAMcompression, put, f, st, sp.abi, &sres) : g_bamsortFns.finish(g_bamsortSorter, P.outBAMcompression, put, f, st);
             std::string e; bgzfEof(e); fwrite(e.data(), 1, e.size(), f);
             if (toStdout) fflush(stdout); else fclose(f);
             const size_t appends = sortAppendBytes.size();
             coordChunks.clear(); coordKeys.clear(); sortAppendBytes.clear();
-            if (rc) return std::string("EXITING because of fatal ERROR: --gpuBAMsort Device: ") + g_bamsortFns.last_error();
+            if (rc) return sig ? std::string("EXITING because of fatal ERROR: --gpuSignal Device: ") + sig->last_error() : std::string("EXITING because of fatal ERROR: --gpuBAMsort Device: ") + g_bamsortFns.last_error();
             sortCounts[0] = st[0]; sortCounts[1] = st[1];
+            std::string werr;
+            if (sig) {
+                const auto t0 = std::chrono::steady_clock::now();
+                werr = signalFromRuns(P, chrName, chrLength, P.outFileNamePrefix + "Signal", &sres);
+                const uint64_t nsDev = sres.stats[4] + sres.stats[5] + sres.stats[6] + sres.stats[7];
+                signalCounts[0] = 1; signalCounts[1] = sres.stats[0]; signalCounts[2] = sres.stats[1]; signalCounts[3] = sres.stats[3];
+                signalCounts[4] = nsDev + (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+                signalCounts[5] = sres.stats[4]; signalCounts[6] = sres.stats[5]; signalCounts[7] = sres.stats[6];
+                if (getenv("STARAMD_HOST_TIMING")) fprintf(stderr, "  signal stage (device): %.2f ms, of which on the device %.2f ms; %llu bytes of runs\n", signalCounts[4] / 1e6, nsDev / 1e6, (unsigned long long)sres.stats[3]);
+            }
             if (FILE *lo = fopen((P.outFileNamePrefix + "Log.out").c_str(), "ab")) {
                 fprintf(lo, "--gpuBAMsort Device: %llu records, %llu bytes of %zu appends ordered on the device\n", (unsigned long long)st[0], (unsigned long long)st[1], appends);
+                if (sig) fprintf(lo, "--gpuSignal Device: %llu records, %llu spans in %llu tiles, %llu bytes of runs from the device\n", (unsigned long long)sres.stats[0], (unsigned long long)sres.stats[1], (unsigned long long)sres.stats[2], (unsigned long long)sres.stats[3]);
                 fclose(lo);
             }
-            return "";
+            if (sig) sig->free_result(&sres);
+            return werr;
         }
         std::vector<uint64_t> ord(coordKeys.size());
         for (uint64_t i = 0; i < ord.size(); i++) ord[i] = i;
@@ -662,7 +683,12 @@ struct Runner {
         if (P.wig.yes && !failed) {                                 // STAR.cpp:275-283: signal tracks from the sorted alignments
             std::vector<const char *> recs(n);
             for (uint64_t i = 0; i < n; i++) { const BamKey &k = K[ord[i]]; recs[i] = coordChunks[k.chunk].data() + k.off; }
+            if (P.gpuSignalDevice)                                  // (the run spilled: its records are here, not on the device)
+                if (FILE *lo = fopen((P.outFileNamePrefix + "Log.out").c_str(), "ab")) { fprintf(lo, "--gpuSignal Device: the sorted records are on the host; the signal tracks are computed on the host\n"); fclose(lo); }
+            const auto t0 = std::chrono::steady_clock::now();
             std::string werr = writeSignal(P, std::vector<std::string>(gi.chrName.begin(), gi.chrName.begin() + gi.view.nChrReal), std::vector<uint64_t>(gi.chrLength.begin(), gi.chrLength.begin() + gi.view.nChrReal), P.outFileNamePrefix + "Signal", recs);
+            signalCounts[1] = n; signalCounts[4] = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+            if (getenv("STARAMD_HOST_TIMING")) fprintf(stderr, "  signal stage (host): %.2f ms\n", signalCounts[4] / 1e6);
             if (!werr.empty()) return werr;
         }
         coordChunks.clear(); coordKeys.clear();
@@ -819,6 +845,16 @@ int sah_bgzf_on_device(void *h) { return ((Runner *)h)->P.gpuBAMdevice ? 1 : 0; 
 void sah_set_bamsort_device(const sah_bamsort_fns *fns, void *sorter) {
     if (fns) staramd::g_bamsortFns = *fns; else staramd::g_bamsortFns = {nullptr, nullptr, nullptr, nullptr};
     staramd::g_bamsortSorter = fns ? sorter : nullptr;
+}
+void sah_set_signal_device(const sah_signal_fns *fns) { staramd::setSignalDeviceFns(fns); }
+int sah_signal_on_device(void *h) { return ((Runner *)h)->P.gpuSignalDevice ? 1 : 0; }
+void sah_signal_counts(void *h, uint64_t out[8]) { for (int i = 0; i < 8; i++) out[i] = ((Runner *)h)->signalCounts[i]; }
+int sah_signal_files_from_runs(int argc, char **argv, int nChr, const char *const *chrName, const uint64_t *chrLength, const void *result, char *errbuf, int errlen) {
+    staramd::RunParams P;
+    std::string e = P.parse(argc, argv);
+    if (e.empty()) e = staramd::signalFromRuns(P, std::vector<std::string>(chrName, chrName + nChr), std::vector<uint64_t>(chrLength, chrLength + nChr), P.outFileNamePrefix + "Signal", result);
+    if (errbuf && errlen > 0) { strncpy(errbuf, e.c_str(), errlen - 1); errbuf[errlen - 1] = 0; }
+    return e.empty() ? 0 : -1;
 }
 int sah_bamsort_on_device(void *h) { return ((Runner *)h)->P.gpuBAMsortDevice ? 1 : 0; }
 uint64_t sah_bamsort_budget(void *h) { return ((Runner *)h)->P.gpuBAMsortHBM; }

@@ -1,7 +1,10 @@
 // signal.cpp -- --outWigType bedGraph | wiggle [read1_5p | read2], --outWigStrand, --outWigNorm, --outWigReferencesPrefix: read coverage ("signal")
 // from the coordinate-sorted alignments, written at the end of an alignReads run as Signal.{Unique,UniqueMultiple}.str{1,2}.out.{bg,wig}.
 //   signalFromBAM     source/signalFromBAM.cpp:5-209   (the reference re-reads its sorted BAM; here the sorted records are still in memory)
+// --gpuSignal Device: the values are computed on the MI355X (include/star_amd_signal.h) and come back as runs; signalFromRuns writes the same files from them.
 #include "host.h"
+#include "../../../include/star_amd_host.h"
+#include "../../../include/star_amd_signal.h"
 #include <cstring>
 #include <cstdio>
 #include <zlib.h>
@@ -129,6 +132,83 @@ std::string writeSignal(const RunParams &P, const std::vector<std::string> &chrN
     return "";
 }
 
+// ---- --gpuSignal Device: the tracks come back from the device as runs (include/star_amd_signal.h); the functions are installed by the driver
+static sah_signal_fns g_signalFns = {nullptr, nullptr, nullptr, nullptr};
+void setSignalDeviceFns(const sah_signal_fns *fns) { if (fns) g_signalFns = *fns; else g_signalFns = {nullptr, nullptr, nullptr, nullptr}; }
+const sah_signal_fns *signalDeviceFns() { return g_signalFns.host_records && g_signalFns.finish_signal && g_signalFns.free_result && g_signalFns.last_error ? &g_signalFns : nullptr; }
+
+void SignalDeviceParams::set(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength) {
+    const WigParams &W = P.wig;
+    len.resize(chrName.size()); wanted.resize(chrName.size());
+    for (size_t i = 0; i < chrName.size(); i++) {
+        len[i] = (uint32_t)chrLength[i];
+        wanted[i] = W.referencesPrefix.empty() || chrName[i].compare(0, W.referencesPrefix.size(), W.referencesPrefix) == 0;
+    }
+    static_assert(sizeof(staramd_signal_params) <= sizeof(abi), "SignalDeviceParams::abi holds a staramd_signal_params");
+    staramd_signal_params sp; memset(&sp, 0, sizeof(sp));
+    sp.type = W.type; sp.strand = W.strand ? 1 : 0; sp.nChr = (uint32_t)chrName.size(); sp.wantNorm = W.norm == 1; sp.chrLength = len.data(); sp.wanted = wanted.data();
+    memcpy(abi, &sp, sizeof(sp));
+}
+
+// The files of writeSignal from runs: same names, same formats, same normFactor arithmetic.  A run is joined with the next of its track when they touch and
+// hold the same value (a tile boundary of the device must not show in a bedGraph line); wiggle prints every position of a run
+std::string signalFromRuns(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength, const std::string &sigFileName, const void *resv) {
+    const staramd_signal_result &R = *(const staramd_signal_result *)resv;
+    const WigParams &W = P.wig;
+    double nMult = 0, nUniq = 0;
+    if (W.norm == 1 && R.norm) for (uint64_t i = 0; i < R.nRecords; i++) { const uint32_t nh = R.norm[i]; if (nh == 1) ++nUniq; else if (nh > 1) nMult += 1.0 / nh; }      // in the records' order, as writeSignal
+    const int sigN = W.strand ? 4 : 2;
+    double normFactor[4] = {1, 1, 1, 1};
+    std::string names[4] = {sigFileName + ".Unique.str1.out", sigFileName + ".UniqueMultiple.str1.out", sigFileName + ".Unique.str2.out", sigFileName + ".UniqueMultiple.str2.out"};
+    FILE *out[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int ii = 0; ii < sigN; ii++) {
+        names[ii] += W.format == 0 ? ".bg" : ".wig";
+        out[ii] = fopen(names[ii].c_str(), "wb");
+        if (!out[ii]) { for (int k = 0; k < ii; k++) fclose(out[k]); return "EXITING because of fatal ERROR: could not create output file " + names[ii]; }
+    }
+    auto closeAll = [&]() { for (int k = 0; k < sigN; k++) fclose(out[k]); };
+    if (R.pastEnd) { closeAll(); return "BUG: alignment extends past chromosome in the signal output"; }
+    if (W.norm == 1) { normFactor[0] = 1.0e6 / nUniq; normFactor[1] = 1.0e6 / (nUniq + nMult); }
+    if (W.strand) { normFactor[2] = normFactor[0]; normFactor[3] = normFactor[1]; }
+    // one line per call, writeSignal's formats put together: "%.5f" under --outWigNorm RPM, "%g" else
+    const std::string num = W.norm == 1 ? "%.5f" : "%g", bgLine = "%s\t%u\t%u\t" + num + "\n", wigLine = "%u\t" + num + "\n";
+    // a track is a file of its own, so the tracks are written side by side (the runs of one track are in order in the array, whatever lies between them)
+    auto writeTrack = [&](int is) {
+        FILE *f = out[is];
+        const double nf = normFactor[is];
+        uint64_t ir = 0;
+        for (uint32_t tid = 0; tid < R.nChr && tid < chrName.size() && tid < chrLength.size(); tid++) {
+            if (!R.chrHas[tid]) continue;
+            const char *chr = chrName[tid].c_str();
+            bool pending = false; uint32_t start = 0, end = 0; double value = 0;
+            auto flush = [&]() {
+                if (!pending) return;
+                // (a run that covers the spare base behind the chromosome is never closed by writeSignal's loop over chrLength + 1 positions: the line ends after the start)
+                if (end <= chrLength[tid]) fprintf(f, bgLine.c_str(), chr, start, end, value * nf); else fprintf(f, "%s\t%u\t", chr, start);
+                pending = false;
+            };
+            if (W.format == 1) fprintf(f, "variableStep chrom=%s\n", chr);
+            for (; ir < R.nRuns && R.runs[ir].tid <= (int32_t)tid; ir++) {
+                const staramd_signal_run &r = R.runs[ir];
+                if (r.tid != (int32_t)tid || (int)r.track != is || r.value == 0) continue;
+                if (W.format == 1) { for (uint32_t ig = r.start; ig < r.end; ig++) fprintf(f, wigLine.c_str(), ig + 1, r.value * nf); continue; }
+                if (pending && end == r.start && memcmp(&value, &r.value, 8) == 0) { end = r.end; continue; }
+                flush();
+                pending = true; start = r.start; end = r.end; value = r.value;
+            }
+            flush();
+        }
+    };
+    if (P.runThreadN > 1 && R.nRuns > 100000) {
+        std::vector<std::thread> th;
+        for (int is = 1; is < sigN; is++) th.emplace_back(writeTrack, is);
+        writeTrack(0);
+        for (auto &t : th) t.join();
+    } else for (int is = 0; is < sigN; is++) writeTrack(is);
+    closeAll();
+    return "";
+}
+
 // --runMode inputAlignmentsFromBAM --inputBAMfile x.bam --outWigType ... (Parameters.cpp:585-592): the same tracks from a coordinate-sorted BAM file.
 // The file is inflated block by block (BGZF = concatenated gzip members) and held in memory; chromosome names and lengths come from its header.
 std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, const std::string &sigFileName) {
@@ -162,6 +242,18 @@ std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, co
         if (p + 4 + bs > d.size()) break;
         recs.push_back(d.data() + p);
         p += 4 + bs;
+    }
+    if (P.gpuSignalDevice) {                                        // --gpuSignal Device: the inflated records go to the device as they are
+        const sah_signal_fns *fns = signalDeviceFns();
+        if (!fns) return SIGNAL_DEVICE_MISSING;
+        std::vector<uint64_t> offsets(recs.size());
+        for (size_t i = 0; i < recs.size(); i++) offsets[i] = (uint64_t)(recs[i] - d.data());
+        SignalDeviceParams sp; sp.set(P, chrName, chrLength);
+        staramd_signal_result res;
+        if (fns->host_records(P.gpuDevice, sp.abi, (const uint8_t *)d.data(), d.size(), offsets.data(), offsets.size(), &res)) return std::string("EXITING because of fatal ERROR: --gpuSignal Device: ") + fns->last_error();
+        std::string e = signalFromRuns(P, chrName, chrLength, sigFileName, &res);
+        fns->free_result(&res);
+        return e;
     }
     return writeSignal(P, chrName, chrLength, sigFileName, recs);
 }

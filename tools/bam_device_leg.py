@@ -5,8 +5,11 @@ compression (STARAMD_HOST_TIMING lines of k_bgzf.hip: host staging copy, H2D, ke
 Then the SortedByCoordinate leg of --gpuBAMsort: compression Host + sort Host, compression Device + sort Host, compression Device + sort Device, alternated,
 --sort-repeats times each (default 2): M pairs/s in the timed region, finishSeconds (the end of the run: writer drained, sorted BAM written, SJ.out.tab)
 and, for the Device sort, the split of staramd_bamsort_finish (its STARAMD_HOST_TIMING line) with the gather kernel's bytes read + written per second.
-  python tools/bam_device_leg.py [--sorted-only] [--sort-repeats N] [--reads N ...bench.py flags] [ENV=V ...]     (GPU box)"""
-import json, os, re, sys, tempfile, time
+With --wig (a --sorted-only form) the leg is that of --gpuSignal: Host sort + host signal and Device sort + --gpuSignal Device, both with --outWigType bedGraph,
+and beside them the same two forms without --outWigType (they run no signal code): finishSeconds, the signal stage's own time on both sides (the
+STARAMD_HOST_TIMING lines of runner.cpp), the device's split per kernel group and the bytes of the runs (k_signal.hip's line).
+  python tools/bam_device_leg.py [--sorted-only [--wig]] [--sort-repeats N] [--reads N ...bench.py flags] [ENV=V ...]     (GPU box)"""
+import hashlib, json, os, re, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench
@@ -56,6 +59,20 @@ def sort_split(text):
             "sink_ms": v[9], "gather_GB_s": round(2 * v[1] / max(v[6], 1e-9), 1)}
 
 
+def signal_split(text):
+    """the signal stage of a run: its time on the host's clock (either side) and, on the device, k_signal.hip's line"""
+    out = {}
+    m = re.search(r"signal stage \((device|host)\): ([0-9.]+) ms", text)
+    if m:
+        out["side"] = m.group(1); out["stage_ms"] = float(m.group(2))
+    m = re.search(r"signal device: (\d+) records, (\d+) pairs, (\d+) tiles, (\d+) runs \(([0-9.]+) MB\): records \+ scan \+ emit ([0-9.]+) ms, sort ([0-9.]+) ms, tiles ([0-9.]+) ms, D2H ([0-9.]+) ms", text)
+    if m:
+        v = m.groups()
+        out.update({"records": int(v[0]), "pairs": int(v[1]), "tiles": int(v[2]), "runs": int(v[3]), "runs_MB": float(v[4]), "records_scan_emit_ms": float(v[5]), "sort_ms": float(v[6]),
+                    "tiles_ms": float(v[7]), "D2H_ms": float(v[8])})
+    return out or None
+
+
 def main():
     env = [a for a in sys.argv[1:] if "=" in a and not a.startswith("-")]
     for a in env:
@@ -63,10 +80,11 @@ def main():
         os.environ[k] = v
     sys.argv = [sys.argv[0]] + [a for a in sys.argv[1:] if a not in env]
     sorted_only = "--sorted-only" in sys.argv
+    wig = "--wig" in sys.argv
     repeats = 2
     if "--sort-repeats" in sys.argv:
         k = sys.argv.index("--sort-repeats"); repeats = int(sys.argv[k + 1]); del sys.argv[k:k + 2]
-    sys.argv = [a for a in sys.argv if a != "--sorted-only"]
+    sys.argv = [a for a in sys.argv if a not in ("--sorted-only", "--wig")]
     args = bench.parse()
     log = lambda s: print("bam_device_leg: " + s, file=sys.stderr, flush=True)
     g, ginfo = bench.build_genome(args, args.genome_mb, log)
@@ -99,24 +117,36 @@ def main():
             row["device_bytes_over_host_bytes"] = round(row["Device"]["bam_bytes"] / row["Host"]["bam_bytes"], 4)
         out[name] = row
     # --gpuBAMsort: the three forms of the SortedByCoordinate run, alternated
-    forms = (("host_host", "Host", "Host"), ("device_compression", "Device", "Host"), ("device_compression_and_sort", "Device", "Device"))
-    leg = {tag: [] for tag, _, _ in forms}
+    forms = (("host_host", "Host", "Host", []), ("device_compression", "Device", "Host", []), ("device_compression_and_sort", "Device", "Device", []))
+    if wig:
+        bg = ["--outWigType", "bedGraph"]
+        forms = (("host_host_signal_host", "Host", "Host", bg), ("device_device_signal_device", "Device", "Device", bg + ["--gpuSignal", "Device"]), forms[0], forms[2])
+    leg = {f[0]: [] for f in forms}
     for rep_i in range(repeats):
-        for tag, comp, srt in forms:
+        for tag, comp, srt, more in forms:
             prefix = os.path.join(rd, "bamsort_%s_" % tag)
             argv = ["--runMode", "alignReads", "--genomeDir", idx, "--readFilesIn"] + fq + ["--outFileNamePrefix", prefix, "--runThreadN", str(threads), "--gpuBatchReads",
                     str(args.reads), "--benchWarmupReads", str(w * args.reads), "--readMapNumber", str((nb + w) * args.reads), "--outSAMtype", "BAM", "SortedByCoordinate",
-                    "--gpuBAMcompression", comp, "--gpuBAMsort", srt]
+                    "--gpuBAMcompression", comp, "--gpuBAMsort", srt] + more
             rc, rep, wall, text = run_captured(argv)
             f = prefix + "Aligned.sortedByCoord.out.bam"
             r = {"exit_code": rc, "Mpairs_s_timed_region": round(int(rep.timedReads) / max(float(rep.timedWall), 1e-9) / 1e6, 4), "finishSeconds": round(float(rep.finishSeconds), 4),
                  "whole_run_s": round(wall, 3), "bam_bytes": os.path.getsize(f) if os.path.isfile(f) else None}
             if srt == "Device":
                 r["finish_split"] = sort_split(text)
+            if more:
+                r["signal"] = signal_split(text)
+                sig = sorted(q for q in os.listdir(rd) if q.startswith("bamsort_%s_Signal." % tag))
+                r["signal_bytes"] = sum(os.path.getsize(os.path.join(rd, q)) for q in sig)
+                h = hashlib.sha256()
+                for q in sig:                                       # the two sides must write the same files
+                    h.update(q[len("bamsort_%s_" % tag):].encode() + b"\0" + open(os.path.join(rd, q), "rb").read())
+                    os.remove(os.path.join(rd, q))
+                r["signal_sha256"] = h.hexdigest()
             leg[tag].append(r)
             if os.path.isfile(f):
                 os.remove(f)
-    out["sorted_by_coordinate_sort_leg"] = leg
+    out["sorted_by_coordinate_signal_leg" if wig else "sorted_by_coordinate_sort_leg"] = leg
     print(json.dumps(out))
 
 
