@@ -1,5 +1,5 @@
 # Build everything that lives in-tree (the .so files travel to the GPU box with gpurun):
-#   star_amd/lib/libstaramd_host.so   host side (index loader, FASTQ batcher, post-map, SAM/SJ writers)  g++
+#   star_amd/lib/libstaramd_host.so   host side (index loader, FASTQ batcher, post-map, SAM/SJ/BAM writers)  g++
 #   star_amd/lib/libstaramd.so        HIP engine behind include/star_amd.h                                hipcc gfx950
 #   star_amd/bin/star_amd             CLI: drop-in for `STAR --runMode alignReads`
 #   oracle/_build/liboracle.so        CPU restatement (test infrastructure)
@@ -36,7 +36,7 @@ engine: star_amd/lib/libstaramd.so
 cli: star_amd/bin/star_amd star_amd/lib/libstaramd_cli.so
 oracle: oracle/_build/liboracle.so oracle/_build/libindex_emul.so oracle/_build/star_amd_oracle_cli oracle/_build/libstaramd_cli_oracle.so oracle/_build/libstaramd_cli_replay.so oracle/_build/libstaramd_emul.so oracle/_build/star_amd_emul_cli
 
-star_amd/lib/libstaramd_host.so: $(HOST_LIB_SRC) star_amd/csrc/host/host.h star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_host.h include/star_amd_signal.h
+star_amd/lib/libstaramd_host.so: $(HOST_LIB_SRC) star_amd/csrc/host/host.h star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_index.h include/star_amd_host.h include/star_amd_bgzf.h include/star_amd_bamsort.h include/star_amd_signal.h
 	@mkdir -p star_amd/lib
 	$(CXX) $(CXXFLAGS) -shared $(HOST_LIB_SRC) -o $@ -lz
 

@@ -1,6 +1,6 @@
 /* star_amd_bamsort.h -- ordering of variable-length byte records under a 128-bit key on the MI355X, and their BGZF compression in that order
  * (star_amd/csrc/engine/k_bamsort.hip, in libstaramd.so).  Made for Aligned.sortedByCoord.out.bam (--gpuBAMsort Device), but it knows nothing of
- * BAM: records are bytes, the order is (g, r, order of appending), exactly the comparator of the host path (Runner::writeSortedBam).
+ * BAM: records are bytes, the order is (g, r, order of appending), exactly the comparator of the host path (CoordSortedBam::sortAndCompress).
  *
  * The records are copied into device memory as they are appended (slabs of STARAMD_BAMSORT_SLAB_BYTES, default 256 MiB; an append goes into one
  * slab as a whole; a larger append gets a slab of its own size).  staramd_bamsort_finish orders the record numbers with two stable radix-sort passes

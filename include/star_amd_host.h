@@ -20,6 +20,8 @@
 #define STAR_AMD_HOST_H
 #include "star_amd.h"
 #include "star_amd_index.h"
+#include "star_amd_bamsort.h"
+#include "star_amd_signal.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -45,12 +47,12 @@ void  sah_set_bgzf_device_fn(int (*fn)(void *user, int level, uint32_t nSeg, con
  * with Device and no sorter installed fails at its first batch.  When append answers 1 (the sorter's budget is used up) the run goes on the Host way:
  * the appends so far are downloaded, the sorter is emptied (finish without a sink), one line goes to Log.out. */
 typedef struct sah_bamsort_fns {
-    int (*append)(void *sorter, const uint8_t *records, uint64_t bytes, const void *keys, uint32_t n);
-    int (*download)(void *sorter, uint32_t iAppend, uint8_t *records);
-    int (*finish)(void *sorter, int level, int (*sink)(void *user, const uint8_t *bytes, uint64_t n), void *user, uint64_t stats[8]);
+    int (*append)(staramd_bamsort *sorter, const uint8_t *records, uint64_t bytes, const staramd_bam_key *keys, uint32_t n);
+    int (*download)(staramd_bamsort *sorter, uint32_t iAppend, uint8_t *records);
+    int (*finish)(staramd_bamsort *sorter, int level, int (*sink)(void *user, const uint8_t *bytes, uint64_t n), void *user, uint64_t stats[8]);
     const char *(*last_error)(void);
 } sah_bamsort_fns;
-void  sah_set_bamsort_device(const sah_bamsort_fns *fns, void *sorter);
+void  sah_set_bamsort_device(const sah_bamsort_fns *fns, staramd_bamsort *sorter);
 int   sah_bamsort_on_device(void *h);                                   /* 1: --gpuBAMsort Device */
 uint64_t sah_bamsort_budget(void *h);                                   /* --gpuBAMsortHBM: what staramd_bamsort_create is to be given */
 /* the coordinate sort of this run so far: [0] records ordered on the device, [1] their bytes (both set by the end of the run), [2] appends the device took,
@@ -62,9 +64,9 @@ void  sah_bam_sort_counts(void *h, uint64_t out[4]);
  * sah_create: install before it.  Process-wide, NULL uninstalls.  A run with Device and nothing installed fails when it comes to the tracks.  A run that
  * spilled to the Host sorter has its records on the host and takes the host's signal code (one line in Log.out says so). */
 typedef struct sah_signal_fns {
-    int (*host_records)(int device, const void *params, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, void *result);
-    int (*finish_signal)(void *sorter, int level, int (*sink)(void *user, const uint8_t *bytes, uint64_t n), void *user, uint64_t stats[8], const void *params, void *result);
-    void (*free_result)(void *result);
+    int (*host_records)(int device, const staramd_signal_params *params, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, staramd_signal_result *result);
+    int (*finish_signal)(staramd_bamsort *sorter, int level, int (*sink)(void *user, const uint8_t *bytes, uint64_t n), void *user, uint64_t stats[8], const staramd_signal_params *params, staramd_signal_result *result);
+    void (*free_result)(staramd_signal_result *result);
     const char *(*last_error)(void);
 } sah_signal_fns;
 void  sah_set_signal_device(const sah_signal_fns *fns);

@@ -134,6 +134,10 @@ __global__ __launch_bounds__(256) void k_bamsort_gather(const uint64_t *__restri
 }
 
 // ---- C ABI --------------------------------------------------------------------------------------------------------------------------------
+#define DEV_HOST_PREFIX "BAM sort on the device: "
+#define DEV_HOST_ROCPRIM
+#include "dev_host.h"
+
 struct staramd_bamsort {
     staramd_bgzf *z = nullptr; int device = 0; hipStream_t st = nullptr, stCopy = nullptr; uint32_t cus = 1;
     uint64_t budget = 0, slabBytes = 256ull << 20, roundBlocks = 8192;
@@ -142,32 +146,15 @@ struct staramd_bamsort {
     std::vector<Slab> slabs; uint64_t allocated = 0;
     std::vector<Append> appends;
     std::vector<uint64_t> g, r, addr; std::vector<uint32_t> len; uint64_t bytes = 0;      // one entry per record, in the order of appending; bytes: the sum of len = the stream's length
-    uint8_t *stage[2] = {nullptr, nullptr}; uint64_t stageCap[2] = {0, 0}; hipEvent_t stageDone[2] = {}; bool stageBusy[2] = {false, false}; uint32_t nextStage = 0;
+    GrowBuf stage[2]; hipEvent_t stageDone[2] = {}; bool stageBusy[2] = {false, false}; uint32_t nextStage = 0;     // page-locked, alternating
     hipEvent_t ev[12] = {};
     BamsortAfterOrder afterOrder = nullptr; void *afterOrderUser = nullptr;              // bamsort_resident.h
 };
 
 namespace {
-thread_local std::string g_err;
-int fail(const std::string &what) { g_err = "BAM sort on the device: " + what; return -1; }
-int failHip(const char *what, hipError_t e) { return fail(std::string(what) + ": " + hipGetErrorString(e)); }
 int failBgzf() { g_err = staramd_bgzf_last_error(); return -1; }
-#define BS_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return failHip(#call, e_); } while (0)
 
 uint64_t envBytes(const char *name, uint64_t dflt) { const char *e = getenv(name); const uint64_t v = e ? strtoull(e, nullptr, 10) : 0; return v ? v : dflt; }
-uint32_t bitsOf(uint64_t v) { uint32_t b = 1; while (b < 64 && (v >> b)) b++; return b; }
-
-void copyBytes(uint8_t *dst, const uint8_t *src, uint64_t n) {                         // a large append on a few threads (a batch's ranges are some MB each)
-    const uint64_t CHUNK = 4u << 20;
-    const unsigned W = (unsigned)std::min<uint64_t>(8, n / (2 * CHUNK));
-    if (W < 2) { if (n) memcpy(dst, src, n); return; }
-    std::atomic<uint64_t> next(0);
-    auto run = [&] { for (uint64_t o; (o = next.fetch_add(CHUNK)) < n;) memcpy(dst + o, src + o, std::min(CHUNK, n - o)); };
-    std::vector<std::thread> th;
-    for (unsigned w = 1; w < W; w++) th.emplace_back(run);
-    run();
-    for (auto &t : th) t.join();
-}
 
 void freeSlabs(staramd_bamsort *s) {
     for (auto &sl : s->slabs) (void)hipFree(sl.d);
@@ -175,25 +162,7 @@ void freeSlabs(staramd_bamsort *s) {
     std::vector<uint64_t>().swap(s->g); std::vector<uint64_t>().swap(s->r); std::vector<uint64_t>().swap(s->addr); std::vector<uint32_t>().swap(s->len);
 }
 int waitUploads(staramd_bamsort *s) {
-    for (int k = 0; k < 2; k++) if (s->stageBusy[k]) { BS_TRY(hipEventSynchronize(s->stageDone[k])); s->stageBusy[k] = false; }
-    return 0;
-}
-
-// device arrays of one finish, freed when it leaves
-struct Work {
-    std::vector<void *> d, h;
-    template <class T> int dev(T *&p, uint64_t n) { void *q = nullptr; BS_TRY(hipMalloc(&q, std::max<uint64_t>(n, 1) * sizeof(T))); d.push_back(q); p = (T *)q; return 0; }
-    template <class T> int host(T *&p, uint64_t n) { void *q = nullptr; BS_TRY(hipHostMalloc(&q, std::max<uint64_t>(n, 1) * sizeof(T), 0)); h.push_back(q); p = (T *)q; return 0; }
-    ~Work() { for (void *p : d) (void)hipFree(p); for (void *p : h) (void)hipHostFree(p); }
-};
-
-int sortPairs(hipStream_t st, uint64_t *&k, uint64_t *&kAlt, uint32_t *&v, uint32_t *&vAlt, uint32_t n, uint32_t bits, void *&tmp, size_t &tmpCap) {
-    rocprim::double_buffer<uint64_t> dk(k, kAlt); rocprim::double_buffer<uint32_t> dv(v, vAlt);
-    size_t need = 0;
-    BS_TRY(rocprim::radix_sort_pairs(nullptr, need, dk, dv, (size_t)n, 0u, bits, st));
-    if (need > tmpCap) { if (tmp) (void)hipFree(tmp); tmp = nullptr; tmpCap = 0; BS_TRY(hipMalloc(&tmp, need)); tmpCap = need; }
-    BS_TRY(rocprim::radix_sort_pairs(tmp, need, dk, dv, (size_t)n, 0u, bits, st));
-    k = dk.current(); kAlt = dk.alternate(); v = dv.current(); vAlt = dv.alternate();
+    for (int k = 0; k < 2; k++) if (s->stageBusy[k]) { DH_TRY(hipEventSynchronize(s->stageDone[k])); s->stageBusy[k] = false; }
     return 0;
 }
 
@@ -211,31 +180,24 @@ int finishOnDevice(staramd_bamsort *s, int level, int (*sink)(void *, const uint
     uint64_t *dG, *dKey, *dKeyAlt, *dAddr, *dLen64, *dSrc; uint32_t *dVal, *dValAlt, *dLen;
     if (wk.dev(dG, n) || wk.dev(dKey, n) || wk.dev(dKeyAlt, n) || wk.dev(dAddr, n) || wk.dev(dLen64, n64 + 1) || wk.dev(dSrc, n) || wk.dev(dVal, n) || wk.dev(dValAlt, n) || wk.dev(dLen, n)) return -1;
     { std::vector<uint64_t> gg(s->g); for (auto &x : gg) if (x == ~0ull) x = unmappedG;
-      BS_TRY(hipMemcpyAsync(dG, gg.data(), n64 * 8, hipMemcpyHostToDevice, st)); BS_TRY(hipStreamSynchronize(st)); }
-    BS_TRY(hipMemcpyAsync(dKey, s->r.data(), n64 * 8, hipMemcpyHostToDevice, st));
-    BS_TRY(hipMemcpyAsync(dAddr, s->addr.data(), n64 * 8, hipMemcpyHostToDevice, st));
-    BS_TRY(hipMemcpyAsync(dLen, s->len.data(), n64 * 4, hipMemcpyHostToDevice, st));
-    const uint32_t gridN = (uint32_t)std::min<uint64_t>((n64 + NT) / NT, 64ull * s->cus);
-    BS_TRY(hipEventRecord(s->ev[0], st));
-    hipLaunchKernelGGL(k_bamsort_iota, dim3(gridN), dim3(NT), 0, st, dVal, n);
-    BS_TRY(hipGetLastError());
-    void *tmp = nullptr; size_t tmpCap = 0;
-    struct FreeTmp { void *&p; ~FreeTmp() { if (p) (void)hipFree(p); } } freeTmp{tmp};
-    if (sortPairs(st, dKey, dKeyAlt, dVal, dValAlt, n, bitsOf(maxR), tmp, tmpCap)) return -1;
-    hipLaunchKernelGGL(k_bamsort_pick, dim3(gridN), dim3(NT), 0, st, dVal, dG, n, dKeyAlt);
-    BS_TRY(hipGetLastError());
+      DH_TRY(hipMemcpyAsync(dG, gg.data(), n64 * 8, hipMemcpyHostToDevice, st)); DH_TRY(hipStreamSynchronize(st)); }
+    DH_TRY(hipMemcpyAsync(dKey, s->r.data(), n64 * 8, hipMemcpyHostToDevice, st));
+    DH_TRY(hipMemcpyAsync(dAddr, s->addr.data(), n64 * 8, hipMemcpyHostToDevice, st));
+    DH_TRY(hipMemcpyAsync(dLen, s->len.data(), n64 * 4, hipMemcpyHostToDevice, st));
+    const uint32_t gridN = gridFor(n64, NT, s->cus);
+    DH_TRY(hipEventRecord(s->ev[0], st));
+    DH_LAUNCH(k_bamsort_iota, dim3(gridN), st, dVal, n);
+    PrimSpace prim;
+    if (prim.sortPairs(st, dKey, dKeyAlt, dVal, dValAlt, n, bitsOf(maxR))) return -1;
+    DH_LAUNCH(k_bamsort_pick, dim3(gridN), st, dVal, dG, n, dKeyAlt);
     std::swap(dKey, dKeyAlt);
-    if (sortPairs(st, dKey, dKeyAlt, dVal, dValAlt, n, bitsOf(std::max(maxG, unmappedG)), tmp, tmpCap)) return -1;
-    BS_TRY(hipEventRecord(s->ev[1], st));
+    if (prim.sortPairs(st, dKey, dKeyAlt, dVal, dValAlt, n, bitsOf(std::max(maxG, unmappedG)))) return -1;
+    DH_TRY(hipEventRecord(s->ev[1], st));
     // ---- where every record goes
-    hipLaunchKernelGGL(k_bamsort_order, dim3(gridN), dim3(NT), 0, st, dVal, dLen, dAddr, n, dLen64, dSrc);
-    BS_TRY(hipGetLastError());
-    {   size_t need = 0;
-        BS_TRY(rocprim::exclusive_scan(nullptr, need, dLen64, dLen64, (uint64_t)0, (size_t)n64 + 1, rocprim::plus<uint64_t>(), st));
-        if (need > tmpCap) { if (tmp) (void)hipFree(tmp); tmp = nullptr; tmpCap = 0; BS_TRY(hipMalloc(&tmp, need)); tmpCap = need; }
-        BS_TRY(rocprim::exclusive_scan(tmp, need, dLen64, dLen64, (uint64_t)0, (size_t)n64 + 1, rocprim::plus<uint64_t>(), st)); }
+    DH_LAUNCH(k_bamsort_order, dim3(gridN), st, dVal, dLen, dAddr, n, dLen64, dSrc);
+    if (prim.exclusiveScan(st, dLen64, (size_t)n64 + 1)) return -1;
     const uint64_t *dDst = dLen64;
-    BS_TRY(hipEventRecord(s->ev[2], st));
+    DH_TRY(hipEventRecord(s->ev[2], st));
     if (s->afterOrder && s->afterOrder(s->afterOrderUser, st, s->cus, dSrc, dDst, n64)) return fail("the pass over the ordered records reported an error");
     // ---- rounds
     const uint64_t total = s->bytes, nbAll = (total + IN_MAX - 1) / IN_MAX, RB = std::min(s->roundBlocks, nbAll), rounds = (nbAll + RB - 1) / RB;
@@ -248,36 +210,35 @@ int finishOnDevice(staramd_bamsort *s, int level, int (*sink)(void *, const uint
     std::vector<uint64_t> blkOff(RB); std::vector<uint32_t> blkLen(RB, IN_MAX), blkLenLast(RB, IN_MAX);
     for (uint64_t b = 0; b < RB; b++) blkOff[b] = b * IN_MAX;
     blkLenLast[nbLast - 1] = (uint32_t)(total - (nbAll - 1) * IN_MAX);
-    BS_TRY(hipMemcpyAsync(dBlkOff, blkOff.data(), RB * 8, hipMemcpyHostToDevice, st));
-    BS_TRY(hipMemcpyAsync(dBlkLen, blkLen.data(), RB * 4, hipMemcpyHostToDevice, st));
-    BS_TRY(hipMemcpyAsync(dBlkLenLast, blkLenLast.data(), RB * 4, hipMemcpyHostToDevice, st));
-    BS_TRY(hipStreamSynchronize(st));
+    DH_TRY(hipMemcpyAsync(dBlkOff, blkOff.data(), RB * 8, hipMemcpyHostToDevice, st));
+    DH_TRY(hipMemcpyAsync(dBlkLen, blkLen.data(), RB * 4, hipMemcpyHostToDevice, st));
+    DH_TRY(hipMemcpyAsync(dBlkLenLast, blkLenLast.data(), RB * 4, hipMemcpyHostToDevice, st));
+    DH_TRY(hipStreamSynchronize(st));
     float msSort = 0, msScan = 0, msGather = 0, msDeflate = 0, msD2H = 0; double sSink = 0; uint64_t outBytes = 0;
     (void)hipEventElapsedTime(&msSort, s->ev[0], s->ev[1]); (void)hipEventElapsedTime(&msScan, s->ev[1], s->ev[2]);
     auto launchRound = [&](uint64_t k) -> int {          // events 3 * parity + 3 ..: before the gather, between gather and deflate, after the deflate
         const int p = (int)(k & 1);
         const uint64_t start = k * roundCap, bytes = std::min(roundCap, total - start), nb = k + 1 == rounds ? nbLast : RB;
         const uint64_t nTiles = (bytes + TILE - 1) / TILE;
-        BS_TRY(hipEventRecord(s->ev[3 + 3 * p], st));
-        hipLaunchKernelGGL(k_bamsort_gather, dim3((uint32_t)std::min<uint64_t>(nTiles, 4ull * s->cus)), dim3(NT), 0, st, dDst, (const uint64_t *)dSrc, n64, start, bytes, dRound);
-        BS_TRY(hipGetLastError());
-        BS_TRY(hipEventRecord(s->ev[4 + 3 * p], st));
+        DH_TRY(hipEventRecord(s->ev[3 + 3 * p], st));
+        DH_LAUNCH(k_bamsort_gather, dim3((uint32_t)std::min<uint64_t>(nTiles, 4ull * s->cus)), st, dDst, (const uint64_t *)dSrc, n64, start, bytes, dRound);
+        DH_TRY(hipEventRecord(s->ev[4 + 3 * p], st));
         if (bgzfCompressResident(s->z, dRound, dBlkOff, k + 1 == rounds ? dBlkLenLast : dBlkLen, (uint32_t)nb, level, dOut[p], dOff[p])) return failBgzf();
-        BS_TRY(hipMemcpyAsync(hTot[p], dOff[p] + nb, 8, hipMemcpyDeviceToHost, st));
-        BS_TRY(hipEventRecord(s->ev[5 + 3 * p], st));
+        DH_TRY(hipMemcpyAsync(hTot[p], dOff[p] + nb, 8, hipMemcpyDeviceToHost, st));
+        DH_TRY(hipEventRecord(s->ev[5 + 3 * p], st));
         return 0;
     };
     if (launchRound(0)) return -1;
     for (uint64_t k = 0; k < rounds; k++) {
         const int p = (int)(k & 1);
         if (k + 1 < rounds && launchRound(k + 1)) return -1;
-        BS_TRY(hipEventSynchronize(s->ev[5 + 3 * p]));
+        DH_TRY(hipEventSynchronize(s->ev[5 + 3 * p]));
         const uint64_t got = *hTot[p];
         if (got > outCap) return fail("device output larger than its bound");
-        BS_TRY(hipEventRecord(s->ev[9], s->stCopy));
-        BS_TRY(hipMemcpyAsync(hOut[p], dOut[p], got, hipMemcpyDeviceToHost, s->stCopy));
-        BS_TRY(hipEventRecord(s->ev[10], s->stCopy));
-        BS_TRY(hipStreamSynchronize(s->stCopy));
+        DH_TRY(hipEventRecord(s->ev[9], s->stCopy));
+        DH_TRY(hipMemcpyAsync(hOut[p], dOut[p], got, hipMemcpyDeviceToHost, s->stCopy));
+        DH_TRY(hipEventRecord(s->ev[10], s->stCopy));
+        DH_TRY(hipStreamSynchronize(s->stCopy));
         float a = 0, b = 0, c = 0;
         (void)hipEventElapsedTime(&a, s->ev[3 + 3 * p], s->ev[4 + 3 * p]); (void)hipEventElapsedTime(&b, s->ev[4 + 3 * p], s->ev[5 + 3 * p]); (void)hipEventElapsedTime(&c, s->ev[9], s->ev[10]);
         msGather += a; msDeflate += b; msD2H += c;
@@ -286,7 +247,7 @@ int finishOnDevice(staramd_bamsort *s, int level, int (*sink)(void *, const uint
         sSink += std::chrono::duration<double>(Clock::now() - t0).count();
         outBytes += got;
     }
-    BS_TRY(hipStreamSynchronize(st));
+    DH_TRY(hipStreamSynchronize(st));
     if (stats) { stats[0] = n; stats[1] = total; stats[2] = rounds; stats[3] = outBytes; stats[4] = (uint64_t)(msSort * 1e6); stats[5] = (uint64_t)(msGather * 1e6);
                  stats[6] = (uint64_t)(msDeflate * 1e6); stats[7] = (uint64_t)(sSink * 1e9); }
     static const bool timing = getenv("STARAMD_HOST_TIMING") != nullptr;
@@ -327,7 +288,7 @@ void staramd_bamsort_destroy(staramd_bamsort *s) {
     if (s->st) (void)hipStreamSynchronize(s->st);
     if (s->stCopy) (void)hipStreamSynchronize(s->stCopy);
     freeSlabs(s);
-    for (auto &p : s->stage) if (p) (void)hipHostFree(p);
+    for (auto &b : s->stage) b.release();
     for (auto &x : s->stageDone) if (x) (void)hipEventDestroy(x);
     for (auto &x : s->ev) if (x) (void)hipEventDestroy(x);
     if (s->stCopy) (void)hipStreamDestroy(s->stCopy);
@@ -338,8 +299,8 @@ int staramd_bamsort_append(staramd_bamsort *s, const uint8_t *records, uint64_t 
     if (!s) return fail("no sorter");
     if (s->g.size() + (uint64_t)n > 0xffffffffull) return fail("more than 2^32 - 1 records");
     for (uint32_t i = 0; i < n; i++) if (keys[i].off > bytes || keys[i].len > bytes - keys[i].off) return fail("record " + std::to_string(i) + " of an append lies outside its " + std::to_string(bytes) + " bytes");
-    BS_TRY(hipSetDevice(s->device));
-    if (s->budget == 0) { size_t fr = 0, tot = 0; BS_TRY(hipMemGetInfo(&fr, &tot)); s->budget = std::max<uint64_t>(1, fr / 2); }
+    DH_TRY(hipSetDevice(s->device));
+    if (s->budget == 0) { size_t fr = 0, tot = 0; DH_TRY(hipMemGetInfo(&fr, &tot)); s->budget = std::max<uint64_t>(1, fr / 2); }
     // the slab: the last one when the append fits behind what it holds, else a new one within the budget
     staramd_bamsort::Slab *sl = s->slabs.empty() ? nullptr : &s->slabs.back();
     if (!sl || sl->cap - sl->used < bytes) {
@@ -356,17 +317,11 @@ int staramd_bamsort_append(staramd_bamsort *s, const uint8_t *records, uint64_t 
     uint8_t *dst = sl->d + sl->used;
     if (bytes) {
         const uint32_t k = s->nextStage; s->nextStage ^= 1;
-        if (s->stageBusy[k]) { BS_TRY(hipEventSynchronize(s->stageDone[k])); s->stageBusy[k] = false; }
-        if (s->stageCap[k] < bytes) {
-            if (s->stage[k]) (void)hipHostFree(s->stage[k]);
-            s->stage[k] = nullptr; s->stageCap[k] = 0;
-            const uint64_t cap = std::max<uint64_t>(bytes + bytes / 4, 1u << 20);
-            BS_TRY(hipHostMalloc((void **)&s->stage[k], cap, 0));
-            s->stageCap[k] = cap;
-        }
-        copyBytes(s->stage[k], records, bytes);
-        BS_TRY(hipMemcpyAsync(dst, s->stage[k], bytes, hipMemcpyHostToDevice, s->st));
-        BS_TRY(hipEventRecord(s->stageDone[k], s->st));
+        if (s->stageBusy[k]) { DH_TRY(hipEventSynchronize(s->stageDone[k])); s->stageBusy[k] = false; }
+        if (s->stage[k].grow(bytes, false)) return -1;
+        copyPieces({{s->stage[k].h, records, bytes}}, bytes);           // (a batch's ranges are some MB each)
+        DH_TRY(hipMemcpyAsync(dst, s->stage[k].h, bytes, hipMemcpyHostToDevice, s->st));
+        DH_TRY(hipEventRecord(s->stageDone[k], s->st));
         s->stageBusy[k] = true;
     }
     sl->used += bytes;
@@ -379,10 +334,10 @@ int staramd_bamsort_append(staramd_bamsort *s, const uint8_t *records, uint64_t 
 int staramd_bamsort_download(staramd_bamsort *s, uint32_t iAppend, uint8_t *records) {
     if (!s) return fail("no sorter");
     if (iAppend >= s->appends.size()) return fail("append " + std::to_string(iAppend) + " of " + std::to_string(s->appends.size()));
-    BS_TRY(hipSetDevice(s->device));
+    DH_TRY(hipSetDevice(s->device));
     if (waitUploads(s)) return -1;
     const staramd_bamsort::Append &a = s->appends[iAppend];
-    if (a.bytes) BS_TRY(hipMemcpy(records, a.d, a.bytes, hipMemcpyDeviceToHost));
+    if (a.bytes) DH_TRY(hipMemcpy(records, a.d, a.bytes, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -392,8 +347,7 @@ int staramd_bamsort_finish(staramd_bamsort *s, int level, int (*sink)(void *user
     (void)hipSetDevice(s->device);
     int rc = waitUploads(s);
     if (rc == 0 && sink) {
-        if (level < -1 || level > 9) rc = fail("compression level " + std::to_string(level) + " is not in -1..9");
-        else {
+        if ((rc = checkLevel(level)) == 0) {
             bgzfResidentLock(s->z);
             rc = finishOnDevice(s, level, sink, user, stats);
             (void)hipStreamSynchronize(s->st); (void)hipStreamSynchronize(s->stCopy);

@@ -500,77 +500,39 @@ __global__ __launch_bounds__(256) void k_bgzf_compact(const uint8_t *slots, cons
 }
 
 // ---- C ABI --------------------------------------------------------------------------------------------------------------------------------
+#define DEV_HOST_PREFIX "BGZF compression on the device: "
+#include "dev_host.h"
+
 struct staramd_bgzf {
     int device = 0; hipStream_t st = nullptr; hipEvent_t ev[4] = {};
     uint32_t grid = 1;
     std::mutex mu;
-    uint8_t *dIn = nullptr, *hIn = nullptr; uint64_t capIn = 0;
-    uint8_t *dOut = nullptr, *hOut = nullptr; uint64_t capOut = 0;
+    GrowBuf in, out;        // the segments of a call side by side, and their members
     uint8_t *dSlots = nullptr; uint32_t *dSizes = nullptr, *dBlkLen = nullptr; uint64_t *dOff = nullptr, *dBlkOff = nullptr, *hOff = nullptr; uint64_t capBlk = 0;
     uint32_t *dScratch = nullptr;
 };
 
 namespace {
-thread_local std::string g_err;
-int fail(const std::string &what) { g_err = "BGZF compression on the device: " + what; return -1; }
-int failHip(const char *what, hipError_t e) { return fail(std::string(what) + ": " + hipGetErrorString(e)); }
-#define BZ_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return failHip(#call, e_); } while (0)
-
-int growIn(staramd_bgzf *z, uint64_t bytes) {
-    if (bytes <= z->capIn) return 0;
-    bytes = std::max<uint64_t>(bytes + bytes / 4, 1u << 20);
-    if (z->dIn) { (void)hipFree(z->dIn); z->dIn = nullptr; } if (z->hIn) { (void)hipHostFree(z->hIn); z->hIn = nullptr; } z->capIn = 0;
-    BZ_TRY(hipMalloc((void **)&z->dIn, bytes));
-    BZ_TRY(hipHostMalloc((void **)&z->hIn, bytes, 0));
-    z->capIn = bytes;
-    return 0;
-}
-int growOut(staramd_bgzf *z, uint64_t bytes) {
-    if (bytes <= z->capOut) return 0;
-    bytes = std::max<uint64_t>(bytes + bytes / 4, 1u << 20);
-    if (z->dOut) { (void)hipFree(z->dOut); z->dOut = nullptr; } if (z->hOut) { (void)hipHostFree(z->hOut); z->hOut = nullptr; } z->capOut = 0;
-    BZ_TRY(hipMalloc((void **)&z->dOut, bytes));
-    BZ_TRY(hipHostMalloc((void **)&z->hOut, bytes, 0));
-    z->capOut = bytes;
-    return 0;
-}
 int growBlk(staramd_bgzf *z, uint64_t nb) {
     if (nb <= z->capBlk) return 0;
     nb = std::max<uint64_t>(nb + nb / 4, 64);
     (void)hipFree(z->dSlots); (void)hipFree(z->dSizes); (void)hipFree(z->dBlkLen); (void)hipFree(z->dOff); (void)hipFree(z->dBlkOff); if (z->hOff) (void)hipHostFree(z->hOff);
     z->dSlots = nullptr; z->dSizes = z->dBlkLen = nullptr; z->dOff = z->dBlkOff = z->hOff = nullptr; z->capBlk = 0;
-    BZ_TRY(hipMalloc((void **)&z->dSlots, nb * SLOT));
-    BZ_TRY(hipMalloc((void **)&z->dSizes, nb * 4));
-    BZ_TRY(hipMalloc((void **)&z->dBlkLen, nb * 4));
-    BZ_TRY(hipMalloc((void **)&z->dBlkOff, nb * 8));
-    BZ_TRY(hipMalloc((void **)&z->dOff, (nb + 1) * 8));
-    BZ_TRY(hipHostMalloc((void **)&z->hOff, (nb + 1) * 8, 0));
+    DH_TRY(hipMalloc((void **)&z->dSlots, nb * SLOT));
+    DH_TRY(hipMalloc((void **)&z->dSizes, nb * 4));
+    DH_TRY(hipMalloc((void **)&z->dBlkLen, nb * 4));
+    DH_TRY(hipMalloc((void **)&z->dBlkOff, nb * 8));
+    DH_TRY(hipMalloc((void **)&z->dOff, (nb + 1) * 8));
+    DH_TRY(hipHostMalloc((void **)&z->hOff, (nb + 1) * 8, 0));
     z->capBlk = nb;
     return 0;
-}
-// memcpy of many pieces on up to 8 threads (the staging copies of a batch are a few hundred MB)
-struct Piece { uint8_t *dst; const uint8_t *src; uint64_t n; };
-void copyPieces(const std::vector<Piece> &ps, uint64_t total) {
-    const uint64_t CH = 4u << 20;
-    std::vector<Piece> cut;
-    for (const Piece &p : ps) for (uint64_t o = 0; o < p.n; o += CH) cut.push_back({p.dst + o, p.src + o, std::min(CH, p.n - o)});
-    const unsigned W = (unsigned)std::min<uint64_t>(std::min<uint64_t>(8, cut.size()), std::max<uint64_t>(1, total >> 22));
-    std::atomic<size_t> next(0);
-    auto run = [&] { for (size_t i; (i = next.fetch_add(1)) < cut.size();) memcpy(cut[i].dst, cut[i].src, cut[i].n); };
-    std::vector<std::thread> th;
-    for (unsigned w = 1; w < W; w++) th.emplace_back(run);
-    run();
-    for (auto &t : th) t.join();
 }
 // the three kernels of one call, on the compressor's stream: the one statement of their launch (staramd_bgzf_compress and bgzfCompressResident)
 int launchKernels(staramd_bgzf *z, const uint8_t *dIn, const uint64_t *dBlkOff, const uint32_t *dBlkLen, uint32_t nb, int level, uint8_t *dOut, uint64_t *dOff) {
     const uint32_t grid = std::min(nb, z->grid);
-    hipLaunchKernelGGL(k_bgzf_blocks, dim3(grid), dim3(NT), 0, z->st, dIn, dBlkOff, dBlkLen, nb, level, z->dScratch, z->dSlots, z->dSizes);
-    BZ_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bgzf_scan, dim3(1), dim3(NT), 0, z->st, z->dSizes, nb, dOff);
-    BZ_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_bgzf_compact, dim3(std::min(nb, 4096u)), dim3(NT), 0, z->st, z->dSlots, z->dSizes, dOff, nb, dOut);
-    BZ_TRY(hipGetLastError());
+    DH_LAUNCH(k_bgzf_blocks, dim3(grid), z->st, dIn, dBlkOff, dBlkLen, nb, level, z->dScratch, z->dSlots, z->dSizes);
+    DH_LAUNCH(k_bgzf_scan, dim3(1), z->st, z->dSizes, nb, dOff);
+    DH_LAUNCH(k_bgzf_compact, dim3(std::min(nb, 4096u)), z->st, z->dSlots, z->dSizes, dOff, nb, dOut);
     return 0;
 }
 }  // namespace
@@ -580,11 +542,11 @@ void bgzfResidentInfo(staramd_bgzf *z, int *device, hipStream_t *stream, uint32_
 void bgzfResidentLock(staramd_bgzf *z) { z->mu.lock(); }
 void bgzfResidentUnlock(staramd_bgzf *z) { z->mu.unlock(); }
 int bgzfResidentReserve(staramd_bgzf *z, uint64_t nb) {
-    BZ_TRY(hipSetDevice(z->device));
+    DH_TRY(hipSetDevice(z->device));
     return growBlk(z, nb);
 }
 int bgzfCompressResident(staramd_bgzf *z, const uint8_t *dIn, const uint64_t *dBlkOff, const uint32_t *dBlkLen, uint32_t nb, int level, uint8_t *dOut, uint64_t *dOff) {
-    if (level < -1 || level > 9) return fail("compression level " + std::to_string(level) + " is not in -1..9");
+    if (checkLevel(level)) return -1;
     if (nb == 0 || nb > z->capBlk) return fail("bgzfCompressResident: " + std::to_string(nb) + " blocks, room reserved for " + std::to_string(z->capBlk));
     return launchKernels(z, dIn, dBlkOff, dBlkLen, nb, level, dOut, dOff);
 }
@@ -610,7 +572,7 @@ int staramd_bgzf_create(staramd_bgzf **out, int device, uint64_t initialInputByt
     if ((e = hipMalloc((void **)&z->dScratch, (uint64_t)z->grid * IN_MAX * 8)) != hipSuccess) return bad(failHip("hipMalloc", e));
     if (initialInputBytes) {
         const uint64_t nb = (initialInputBytes + IN_MAX - 1) / IN_MAX;
-        if (growIn(z, initialInputBytes) || growOut(z, staramd_bgzf_bound(initialInputBytes)) || growBlk(z, nb)) return bad(-1);
+        if (z->in.grow(initialInputBytes) || z->out.grow(staramd_bgzf_bound(initialInputBytes)) || growBlk(z, nb)) return bad(-1);
     }
     *out = z;
     return 0;
@@ -620,9 +582,8 @@ void staramd_bgzf_destroy(staramd_bgzf *z) {
     if (!z) return;
     (void)hipSetDevice(z->device);
     if (z->st) (void)hipStreamSynchronize(z->st);
-    (void)hipFree(z->dIn); (void)hipFree(z->dOut); (void)hipFree(z->dSlots); (void)hipFree(z->dSizes); (void)hipFree(z->dBlkLen); (void)hipFree(z->dBlkOff); (void)hipFree(z->dOff); (void)hipFree(z->dScratch);
-    if (z->hIn) (void)hipHostFree(z->hIn);
-    if (z->hOut) (void)hipHostFree(z->hOut);
+    z->in.release(); z->out.release();
+    (void)hipFree(z->dSlots); (void)hipFree(z->dSizes); (void)hipFree(z->dBlkLen); (void)hipFree(z->dBlkOff); (void)hipFree(z->dOff); (void)hipFree(z->dScratch);
     if (z->hOff) (void)hipHostFree(z->hOff);
     for (auto &x : z->ev) if (x) (void)hipEventDestroy(x);
     if (z->st) (void)hipStreamDestroy(z->st);
@@ -632,7 +593,7 @@ void staramd_bgzf_destroy(staramd_bgzf *z) {
 int staramd_bgzf_compress(void *zv, int level, uint32_t nSeg, const uint8_t *const *in, const uint64_t *inLen, uint8_t *out, uint64_t outCap, uint64_t *outLen) {
     staramd_bgzf *z = (staramd_bgzf *)zv;
     if (!z) return fail("no compressor");
-    if (level < -1 || level > 9) return fail("compression level " + std::to_string(level) + " is not in -1..9");
+    if (checkLevel(level)) return -1;
     std::lock_guard<std::mutex> lock(z->mu);
     typedef std::chrono::steady_clock Clock;
     const auto t0 = Clock::now();
@@ -641,34 +602,34 @@ int staramd_bgzf_compress(void *zv, int level, uint32_t nSeg, const uint8_t *con
     if (bound > outCap) return fail("output buffer of " + std::to_string(outCap) + " bytes, " + std::to_string(bound) + " may be needed");
     if (nb == 0) { for (uint32_t s = 0; s < nSeg; s++) outLen[s] = 0; return 0; }
     if (nb > 0xffffffffull) return fail("too many blocks in one call");
-    BZ_TRY(hipSetDevice(z->device));
-    if (growIn(z, total) || growOut(z, bound) || growBlk(z, nb)) return -1;
+    DH_TRY(hipSetDevice(z->device));
+    if (z->in.grow(total) || z->out.grow(bound) || growBlk(z, nb)) return -1;
     std::vector<uint64_t> blkOff(nb); std::vector<uint32_t> blkLen(nb);
     std::vector<Piece> ps;
     uint64_t at = 0, ib = 0;
     for (uint32_t s = 0; s < nSeg; s++) {
-        ps.push_back({z->hIn + at, in[s], inLen[s]});
+        ps.push_back({z->in.h + at, in[s], inLen[s]});
         for (uint64_t o = 0; o < inLen[s]; o += IN_MAX) { blkOff[ib] = at + o; blkLen[ib] = (uint32_t)std::min<uint64_t>(IN_MAX, inLen[s] - o); ib++; }
         at += inLen[s];
     }
     copyPieces(ps, total);
     const auto t1 = Clock::now();
-    BZ_TRY(hipEventRecord(z->ev[0], z->st));
-    BZ_TRY(hipMemcpyAsync(z->dIn, z->hIn, total, hipMemcpyHostToDevice, z->st));
-    BZ_TRY(hipMemcpyAsync(z->dBlkOff, blkOff.data(), nb * 8, hipMemcpyHostToDevice, z->st));
-    BZ_TRY(hipMemcpyAsync(z->dBlkLen, blkLen.data(), nb * 4, hipMemcpyHostToDevice, z->st));
-    BZ_TRY(hipEventRecord(z->ev[1], z->st));
-    if (launchKernels(z, z->dIn, z->dBlkOff, z->dBlkLen, (uint32_t)nb, level, z->dOut, z->dOff)) return -1;
-    BZ_TRY(hipMemcpyAsync(z->hOff, z->dOff, (nb + 1) * 8, hipMemcpyDeviceToHost, z->st));
-    BZ_TRY(hipEventRecord(z->ev[2], z->st));
-    BZ_TRY(hipStreamSynchronize(z->st));
+    DH_TRY(hipEventRecord(z->ev[0], z->st));
+    DH_TRY(hipMemcpyAsync(z->in.d, z->in.h, total, hipMemcpyHostToDevice, z->st));
+    DH_TRY(hipMemcpyAsync(z->dBlkOff, blkOff.data(), nb * 8, hipMemcpyHostToDevice, z->st));
+    DH_TRY(hipMemcpyAsync(z->dBlkLen, blkLen.data(), nb * 4, hipMemcpyHostToDevice, z->st));
+    DH_TRY(hipEventRecord(z->ev[1], z->st));
+    if (launchKernels(z, z->in.d, z->dBlkOff, z->dBlkLen, (uint32_t)nb, level, z->out.d, z->dOff)) return -1;
+    DH_TRY(hipMemcpyAsync(z->hOff, z->dOff, (nb + 1) * 8, hipMemcpyDeviceToHost, z->st));
+    DH_TRY(hipEventRecord(z->ev[2], z->st));
+    DH_TRY(hipStreamSynchronize(z->st));
     const uint64_t outTotal = z->hOff[nb];
     if (outTotal > bound) return fail("device output larger than its bound");
-    BZ_TRY(hipMemcpyAsync(z->hOut, z->dOut, outTotal, hipMemcpyDeviceToHost, z->st));
-    BZ_TRY(hipEventRecord(z->ev[3], z->st));
-    BZ_TRY(hipStreamSynchronize(z->st));
+    DH_TRY(hipMemcpyAsync(z->out.h, z->out.d, outTotal, hipMemcpyDeviceToHost, z->st));
+    DH_TRY(hipEventRecord(z->ev[3], z->st));
+    DH_TRY(hipStreamSynchronize(z->st));
     const auto t2 = Clock::now();
-    copyPieces({{out, z->hOut, outTotal}}, outTotal);
+    copyPieces({{out, z->out.h, outTotal}}, outTotal);
     ib = 0;
     for (uint32_t s = 0; s < nSeg; s++) {
         const uint64_t k = (inLen[s] + IN_MAX - 1) / IN_MAX;

@@ -225,22 +225,11 @@ __global__ __launch_bounds__(256) void k_signal_tiles(const uint64_t *__restrict
 }
 
 // ---- C ABI --------------------------------------------------------------------------------------------------------------------------------
+#define DEV_HOST_PREFIX "signal tracks on the device: "
+#define DEV_HOST_ROCPRIM
+#include "dev_host.h"
+
 namespace {
-thread_local std::string g_err;
-int fail(const std::string &what) { g_err = "signal tracks on the device: " + what; return -1; }
-int failHip(const char *what, hipError_t e) { return fail(std::string(what) + ": " + hipGetErrorString(e)); }
-#define SG_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return failHip(#call, e_); } while (0)
-
-uint32_t bitsOf(uint64_t v) { uint32_t b = 1; while (b < 64 && (v >> b)) b++; return b; }
-
-// device arrays and events of one call, freed when it leaves
-struct Work {
-    std::vector<void *> d; std::vector<hipEvent_t> ev;
-    template <class X> int dev(X *&p, uint64_t n) { void *q = nullptr; SG_TRY(hipMalloc(&q, std::max<uint64_t>(n, 1) * sizeof(X))); d.push_back(q); p = (X *)q; return 0; }
-    int event(hipEvent_t &e) { SG_TRY(hipEventCreate(&e)); ev.push_back(e); return 0; }
-    ~Work() { for (void *p : d) (void)hipFree(p); for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-};
-
 void clearResult(staramd_signal_result *r) { memset(r, 0, sizeof(*r)); }
 int checkParams(const staramd_signal_params *p, staramd_signal_result *out) {
     if (!p || !out) return fail("no parameters or no result");
@@ -251,14 +240,6 @@ int checkParams(const staramd_signal_params *p, staramd_signal_result *out) {
     out->nChr = p->nChr;
     out->chrHas = (uint8_t *)calloc(std::max<uint32_t>(p->nChr, 1), 1);
     if (!out->chrHas) return fail("no host memory for the result");
-    return 0;
-}
-
-template <class X> int scan(hipStream_t st, X *v, uint64_t n, void *&tmp, size_t &tmpCap) {
-    size_t need = 0;
-    SG_TRY(rocprim::exclusive_scan(nullptr, need, v, v, (X)0, (size_t)n, rocprim::plus<X>(), st));
-    if (need > tmpCap) { if (tmp) (void)hipFree(tmp); tmp = nullptr; tmpCap = 0; SG_TRY(hipMalloc(&tmp, need)); tmpCap = need; }
-    SG_TRY(rocprim::exclusive_scan(tmp, need, v, v, (X)0, (size_t)n, rocprim::plus<X>(), st));
     return 0;
 }
 
@@ -276,85 +257,71 @@ int signalOnDevice(hipStream_t st, uint32_t cus, const uint64_t *dAddr, const ui
     uint32_t *dLen, *dWanted, *dNorm = nullptr, *dHas, *dPast; uint64_t *dCnt;
     if (wk.dev(dLen, p->nChr) || wk.dev(dWanted, p->nChr) || wk.dev(dHas, p->nChr) || wk.dev(dPast, 1) || wk.dev(dCnt, n + 1)) return -1;
     if (p->wantNorm && wk.dev(dNorm, n)) return -1;
-    SG_TRY(hipMemcpyAsync(dLen, p->chrLength, (uint64_t)p->nChr * 4, hipMemcpyHostToDevice, st));
-    SG_TRY(hipMemcpyAsync(dWanted, wanted.data(), (uint64_t)p->nChr * 4, hipMemcpyHostToDevice, st));
-    SG_TRY(hipMemsetAsync(dHas, 0, std::max<uint64_t>(p->nChr, 1) * 4, st));
-    SG_TRY(hipMemsetAsync(dPast, 0, 4, st));
+    DH_TRY(hipMemcpyAsync(dLen, p->chrLength, (uint64_t)p->nChr * 4, hipMemcpyHostToDevice, st));
+    DH_TRY(hipMemcpyAsync(dWanted, wanted.data(), (uint64_t)p->nChr * 4, hipMemcpyHostToDevice, st));
+    DH_TRY(hipMemsetAsync(dHas, 0, std::max<uint64_t>(p->nChr, 1) * 4, st));
+    DH_TRY(hipMemsetAsync(dPast, 0, 4, st));
     A.chrLength = dLen; A.wanted = dWanted;
-    auto gridFor = [&](uint64_t items) { return dim3((uint32_t)std::min<uint64_t>((items + NT) / NT, 64ull * cus)); };
-    void *tmp = nullptr; size_t tmpCap = 0;
-    struct FreeTmp { void *&p; ~FreeTmp() { if (p) (void)hipFree(p); } } freeTmp{tmp};
+    PrimSpace prim;
     // ---- records, scan
-    SG_TRY(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(k_signal_records, gridFor(n), dim3(NT), 0, st, dAddr, dDst, n, A, dCnt, dNorm, dHas, dPast);
-    SG_TRY(hipGetLastError());
-    if (scan(st, dCnt, n + 1, tmp, tmpCap)) return -1;
+    DH_TRY(hipEventRecord(ev[0], st));
+    DH_LAUNCH(k_signal_records, dim3(gridFor(n, NT, cus)), st, dAddr, dDst, n, A, dCnt, dNorm, dHas, dPast);
+    if (prim.exclusiveScan(st, dCnt, n + 1)) return -1;
     uint64_t nPairs = 0; uint32_t past = 0;
     std::vector<uint32_t> has(p->nChr);
-    SG_TRY(hipMemcpyAsync(&nPairs, dCnt + n, 8, hipMemcpyDeviceToHost, st));
-    SG_TRY(hipMemcpyAsync(&past, dPast, 4, hipMemcpyDeviceToHost, st));
-    SG_TRY(hipMemcpyAsync(has.data(), dHas, (uint64_t)p->nChr * 4, hipMemcpyDeviceToHost, st));
-    SG_TRY(hipStreamSynchronize(st));
+    DH_TRY(hipMemcpyAsync(&nPairs, dCnt + n, 8, hipMemcpyDeviceToHost, st));
+    DH_TRY(hipMemcpyAsync(&past, dPast, 4, hipMemcpyDeviceToHost, st));
+    DH_TRY(hipMemcpyAsync(has.data(), dHas, (uint64_t)p->nChr * 4, hipMemcpyDeviceToHost, st));
+    DH_TRY(hipStreamSynchronize(st));
     for (uint32_t i = 0; i < p->nChr; i++) out->chrHas[i] = has[i] ? 1 : 0;
     if (dNorm) {
         out->norm = (uint32_t *)malloc(n * 4);
         if (!out->norm) return fail("no host memory for the result");
-        SG_TRY(hipMemcpyAsync(out->norm, dNorm, n * 4, hipMemcpyDeviceToHost, st));
+        DH_TRY(hipMemcpyAsync(out->norm, dNorm, n * 4, hipMemcpyDeviceToHost, st));
     }
     out->stats[1] = nPairs;
-    if (past) { out->pastEnd = 1; SG_TRY(hipStreamSynchronize(st)); return 0; }
+    if (past) { out->pastEnd = 1; DH_TRY(hipStreamSynchronize(st)); return 0; }
     uint64_t nTiles = 0, nRunsTotal = 0;
     float msRec = 0, msSort = 0, msTiles = 0, msBack = 0;
     if (nPairs) {
         // ---- emit, sort
         uint64_t *dKey, *dKeyAlt, *dVal, *dValAlt;
         if (wk.dev(dKey, nPairs + 1) || wk.dev(dKeyAlt, nPairs + 1) || wk.dev(dVal, nPairs + 1) || wk.dev(dValAlt, nPairs + 1)) return -1;
-        hipLaunchKernelGGL(k_signal_emit, gridFor(n), dim3(NT), 0, st, dAddr, dDst, n, A, (const uint64_t *)dCnt, dKey, dVal);
-        SG_TRY(hipGetLastError());
-        SG_TRY(hipEventRecord(ev[1], st));
-        {   rocprim::double_buffer<uint64_t> dk(dKey, dKeyAlt), dv(dVal, dValAlt);
-            const uint32_t bits = A.tileBits + bitsOf(p->nChr ? p->nChr - 1 : 0);
-            size_t need = 0;
-            SG_TRY(rocprim::radix_sort_pairs(nullptr, need, dk, dv, (size_t)nPairs, 0u, bits, st));
-            if (need > tmpCap) { if (tmp) (void)hipFree(tmp); tmp = nullptr; tmpCap = 0; SG_TRY(hipMalloc(&tmp, need)); tmpCap = need; }
-            SG_TRY(rocprim::radix_sort_pairs(tmp, need, dk, dv, (size_t)nPairs, 0u, bits, st));
-            dKey = dk.current(); dKeyAlt = dk.alternate(); dVal = dv.current(); dValAlt = dv.alternate(); }
-        SG_TRY(hipEventRecord(ev[2], st));
+        DH_LAUNCH(k_signal_emit, dim3(gridFor(n, NT, cus)), st, dAddr, dDst, n, A, (const uint64_t *)dCnt, dKey, dVal);
+        DH_TRY(hipEventRecord(ev[1], st));
+        if (prim.sortPairs(st, dKey, dKeyAlt, dVal, dValAlt, nPairs, A.tileBits + bitsOf(p->nChr ? p->nChr - 1 : 0))) return -1;
+        DH_TRY(hipEventRecord(ev[2], st));
         // ---- occupied tiles: the alternate buffers of the sort (whichever they are now: all four have the spare entry) hold head flags / ranks and tile starts
         uint64_t *dRank = dKeyAlt, *dStart = dValAlt;
-        hipLaunchKernelGGL(k_signal_heads, gridFor(nPairs), dim3(NT), 0, st, (const uint64_t *)dKey, nPairs, dRank);
-        SG_TRY(hipGetLastError());
-        if (scan(st, dRank, nPairs + 1, tmp, tmpCap)) return -1;
-        hipLaunchKernelGGL(k_signal_tile_starts, gridFor(nPairs), dim3(NT), 0, st, (const uint64_t *)dKey, (const uint64_t *)dRank, nPairs, dStart);
-        SG_TRY(hipGetLastError());
-        SG_TRY(hipMemcpyAsync(&nTiles, dRank + nPairs, 8, hipMemcpyDeviceToHost, st));
-        SG_TRY(hipStreamSynchronize(st));
+        DH_LAUNCH(k_signal_heads, dim3(gridFor(nPairs, NT, cus)), st, (const uint64_t *)dKey, nPairs, dRank);
+        if (prim.exclusiveScan(st, dRank, nPairs + 1)) return -1;
+        DH_LAUNCH(k_signal_tile_starts, dim3(gridFor(nPairs, NT, cus)), st, (const uint64_t *)dKey, (const uint64_t *)dRank, nPairs, dStart);
+        DH_TRY(hipMemcpyAsync(&nTiles, dRank + nPairs, 8, hipMemcpyDeviceToHost, st));
+        DH_TRY(hipStreamSynchronize(st));
         // ---- tiles: count, scan, fill
         uint64_t *dRuns64 = dRank;                                  // the ranks are done with: nTiles + 1 <= nPairs + 1 counts
         const dim3 gridT((uint32_t)std::min<uint64_t>(nTiles, 8ull * cus));
-        SG_TRY(hipMemsetAsync(dRuns64 + nTiles, 0, 8, st));
-        hipLaunchKernelGGL(k_signal_tiles, gridT, dim3(NT), 0, st, (const uint64_t *)dKey, (const uint64_t *)dVal, (const uint64_t *)dStart, nTiles, A.tileBits, A.strand, 0, dRuns64, (staramd_signal_run *)nullptr);
-        SG_TRY(hipGetLastError());
-        if (scan(st, dRuns64, nTiles + 1, tmp, tmpCap)) return -1;
-        SG_TRY(hipMemcpyAsync(&nRunsTotal, dRuns64 + nTiles, 8, hipMemcpyDeviceToHost, st));
-        SG_TRY(hipStreamSynchronize(st));
+        DH_TRY(hipMemsetAsync(dRuns64 + nTiles, 0, 8, st));
+        DH_LAUNCH(k_signal_tiles, gridT, st, (const uint64_t *)dKey, (const uint64_t *)dVal, (const uint64_t *)dStart, nTiles, A.tileBits, A.strand, 0, dRuns64, (staramd_signal_run *)nullptr);
+        if (prim.exclusiveScan(st, dRuns64, nTiles + 1)) return -1;
+        DH_TRY(hipMemcpyAsync(&nRunsTotal, dRuns64 + nTiles, 8, hipMemcpyDeviceToHost, st));
+        DH_TRY(hipStreamSynchronize(st));
         staramd_signal_run *dRuns = nullptr;
         if (nRunsTotal) {
             if (wk.dev(dRuns, nRunsTotal)) return -1;
-            hipLaunchKernelGGL(k_signal_tiles, gridT, dim3(NT), 0, st, (const uint64_t *)dKey, (const uint64_t *)dVal, (const uint64_t *)dStart, nTiles, A.tileBits, A.strand, 1, dRuns64, dRuns);
-            SG_TRY(hipGetLastError());
+            DH_LAUNCH(k_signal_tiles, gridT, st, (const uint64_t *)dKey, (const uint64_t *)dVal, (const uint64_t *)dStart, nTiles, A.tileBits, A.strand, 1, dRuns64, dRuns);
         }
-        SG_TRY(hipEventRecord(ev[3], st));
+        DH_TRY(hipEventRecord(ev[3], st));
         if (nRunsTotal) {
             out->runs = (staramd_signal_run *)malloc(nRunsTotal * sizeof(staramd_signal_run));
             if (!out->runs) return fail("no host memory for the result");
-            SG_TRY(hipMemcpyAsync(out->runs, dRuns, nRunsTotal * sizeof(staramd_signal_run), hipMemcpyDeviceToHost, st));
+            DH_TRY(hipMemcpyAsync(out->runs, dRuns, nRunsTotal * sizeof(staramd_signal_run), hipMemcpyDeviceToHost, st));
             out->nRuns = nRunsTotal;
         }
-        SG_TRY(hipEventRecord(ev[4], st));
-        SG_TRY(hipStreamSynchronize(st));
+        DH_TRY(hipEventRecord(ev[4], st));
+        DH_TRY(hipStreamSynchronize(st));
         (void)hipEventElapsedTime(&msRec, ev[0], ev[1]); (void)hipEventElapsedTime(&msSort, ev[1], ev[2]); (void)hipEventElapsedTime(&msTiles, ev[2], ev[3]); (void)hipEventElapsedTime(&msBack, ev[3], ev[4]);
-    } else SG_TRY(hipStreamSynchronize(st));
+    } else DH_TRY(hipStreamSynchronize(st));
     out->stats[2] = nTiles; out->stats[3] = nRunsTotal * sizeof(staramd_signal_run);
     out->stats[4] = (uint64_t)(msRec * 1e6); out->stats[5] = (uint64_t)(msSort * 1e6); out->stats[6] = (uint64_t)(msTiles * 1e6); out->stats[7] = (uint64_t)(msBack * 1e6);
     static const bool timing = getenv("STARAMD_HOST_TIMING") != nullptr;
@@ -404,10 +371,10 @@ int staramd_signal_host_records(int device, const staramd_signal_params *p, cons
         if (rc == 0) {
             for (uint64_t i = 0; i < n; i++) addr[i] = (uint64_t)(uintptr_t)(dBytes + offsets[i]);
             auto run = [&]() -> int {
-                if (nBytes) SG_TRY(hipMemcpyAsync(dBytes, bytes, nBytes, hipMemcpyHostToDevice, st));
-                if (n) SG_TRY(hipMemcpyAsync(dAddr, addr.data(), n * 8, hipMemcpyHostToDevice, st));
-                SG_TRY(hipMemcpyAsync(dDst, dst.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
-                SG_TRY(hipStreamSynchronize(st));
+                if (nBytes) DH_TRY(hipMemcpyAsync(dBytes, bytes, nBytes, hipMemcpyHostToDevice, st));
+                if (n) DH_TRY(hipMemcpyAsync(dAddr, addr.data(), n * 8, hipMemcpyHostToDevice, st));
+                DH_TRY(hipMemcpyAsync(dDst, dst.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+                DH_TRY(hipStreamSynchronize(st));
                 return signalOnDevice(st, (uint32_t)std::max(1, prop.multiProcessorCount), dAddr, dDst, n, p, out);
             };
             rc = run();

@@ -40,30 +40,25 @@
 #include "../../../include/star_amd_index.h"
 #include "../../../include/star_amd_cli.h"
 #include "../../../include/star_amd_async.h"
-#include "../../../include/star_amd_bgzf.h"
-#include "../../../include/star_amd_bamsort.h"
-#include "../../../include/star_amd_signal.h"
 
 // the device BGZF compressor (k_bgzf.hip) is in the shipped engine library only: the front ends linked against the oracle / the emulated engine run
 // without it, and a run that asks for it there fails at its first batch (sah_set_bgzf_device_fn)
-extern "C" {
-__attribute__((weak)) int staramd_bgzf_create(staramd_bgzf **out, int device, uint64_t initialInputBytes);
-__attribute__((weak)) int staramd_bgzf_compress(void *z, int level, uint32_t nSeg, const uint8_t *const *in, const uint64_t *inLen, uint8_t *out, uint64_t outCap, uint64_t *outLen);
-__attribute__((weak)) void staramd_bgzf_destroy(staramd_bgzf *z);
-__attribute__((weak)) const char *staramd_bgzf_last_error(void);
+#pragma weak staramd_bgzf_create
+#pragma weak staramd_bgzf_compress
+#pragma weak staramd_bgzf_destroy
+#pragma weak staramd_bgzf_last_error
 // likewise the device sorter of Aligned.sortedByCoord.out.bam (k_bamsort.hip, sah_set_bamsort_device)
-__attribute__((weak)) int staramd_bamsort_create(staramd_bamsort **out, staramd_bgzf *z, uint64_t hbmBudgetBytes);
-__attribute__((weak)) int staramd_bamsort_append(staramd_bamsort *s, const uint8_t *records, uint64_t bytes, const staramd_bam_key *keys, uint32_t n);
-__attribute__((weak)) int staramd_bamsort_download(staramd_bamsort *s, uint32_t iAppend, uint8_t *records);
-__attribute__((weak)) int staramd_bamsort_finish(staramd_bamsort *s, int level, int (*sink)(void *user, const uint8_t *bytes, uint64_t n), void *user, uint64_t stats[8]);
-__attribute__((weak)) void staramd_bamsort_destroy(staramd_bamsort *s);
-__attribute__((weak)) const char *staramd_bamsort_last_error(void);
+#pragma weak staramd_bamsort_create
+#pragma weak staramd_bamsort_append
+#pragma weak staramd_bamsort_download
+#pragma weak staramd_bamsort_finish
+#pragma weak staramd_bamsort_destroy
+#pragma weak staramd_bamsort_last_error
 // and the signal tracks on the device (k_signal.hip, sah_set_signal_device)
-__attribute__((weak)) int staramd_signal_host_records(int device, const staramd_signal_params *p, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, staramd_signal_result *out);
-__attribute__((weak)) int staramd_bamsort_finish_signal(staramd_bamsort *s, int level, int (*sink)(void *user, const uint8_t *bytes, uint64_t n), void *user, uint64_t stats[8], const staramd_signal_params *p, staramd_signal_result *out);
-__attribute__((weak)) void staramd_signal_free(staramd_signal_result *r);
-__attribute__((weak)) const char *staramd_signal_last_error(void);
-}
+#pragma weak staramd_signal_host_records
+#pragma weak staramd_bamsort_finish_signal
+#pragma weak staramd_signal_free
+#pragma weak staramd_signal_last_error
 
 namespace {
 typedef std::chrono::steady_clock Clock;
@@ -255,11 +250,7 @@ struct Engines {
         }
         if (sortDev && bgzf) {
             if (staramd_bamsort_create(&bamsort, bgzf, sah_bamsort_budget(h))) { fprintf(stderr, "\nEXITING because of FATAL ERROR: cannot initialise the BAM sorter on device %d: %s\n", devices[0], staramd_bamsort_last_error()); return 105; }
-            static const sah_bamsort_fns fns = {
-                [](void *s, const uint8_t *rec, uint64_t bytes, const void *keys, uint32_t n) { return staramd_bamsort_append((staramd_bamsort *)s, rec, bytes, (const staramd_bam_key *)keys, n); },
-                [](void *s, uint32_t i, uint8_t *rec) { return staramd_bamsort_download((staramd_bamsort *)s, i, rec); },
-                [](void *s, int level, int (*sink)(void *, const uint8_t *, uint64_t), void *user, uint64_t *stats) { return staramd_bamsort_finish((staramd_bamsort *)s, level, sink, user, stats); },
-                staramd_bamsort_last_error};
+            static const sah_bamsort_fns fns = {staramd_bamsort_append, staramd_bamsort_download, staramd_bamsort_finish, staramd_bamsort_last_error};
             sah_set_bamsort_device(&fns, bamsort);
         }
         owners.assign(ctx.begin(), ctx.begin() + nOwners);
@@ -534,11 +525,7 @@ int staramd_cli_main(int argc, char **argv, const staramd_cli_hooks *hooks, star
     CliFlags flags = splitFlags(argc, argv);
     if (!getenv("STARAMD_SJDB_HOST")) sah_set_sjdb_device_fn(staramd_sjdb_insert, flags.devices.empty() ? 0 : flags.devices[0]);   // junction insertion on the device
     if (staramd_signal_host_records && staramd_bamsort_finish_signal && staramd_signal_free && staramd_signal_last_error) {      // --gpuSignal Device; before sah_create, where the tool mode runs
-        static const sah_signal_fns fns = {
-            [](int device, const void *p, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, void *res) { return staramd_signal_host_records(device, (const staramd_signal_params *)p, bytes, nBytes, offsets, n, (staramd_signal_result *)res); },
-            [](void *s, int level, int (*sink)(void *, const uint8_t *, uint64_t), void *user, uint64_t *stats, const void *p, void *res) { return staramd_bamsort_finish_signal((staramd_bamsort *)s, level, sink, user, stats, (const staramd_signal_params *)p, (staramd_signal_result *)res); },
-            [](void *res) { staramd_signal_free((staramd_signal_result *)res); },
-            staramd_signal_last_error};
+        static const sah_signal_fns fns = {staramd_signal_host_records, staramd_bamsort_finish_signal, staramd_signal_free, staramd_signal_last_error};
         sah_set_signal_device(&fns);
     }
     LoadLock loadLock;

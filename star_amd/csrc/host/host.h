@@ -20,7 +20,7 @@
 #include <thread>
 #include "../../../include/star_amd.h"
 #include "../../../include/star_amd_index.h"
-struct sah_signal_fns;                  // include/star_amd_host.h
+#include "../../../include/star_amd_host.h"
 
 namespace staramd {
 // CPU seconds per pipeline stage (thread CPU clocks: what a stage COSTS, beside the wall-clock busy times that say how long it TAKES): every thread of the front end
@@ -73,6 +73,9 @@ struct GenomeIndex {
     // returns empty string on success, else the error text
     std::string load(const std::string &genomeDir);
     void refreshView();       // re-point `view` at the vectors after they were rewritten (sjdb insertion)
+    // names and lengths of the real chromosomes (the first view.nChrReal entries; junction inserts follow), as the signal writers take them
+    std::vector<std::string> realChrNames() const { return std::vector<std::string>(chrName.begin(), chrName.begin() + view.nChrReal); }
+    std::vector<uint64_t> realChrLengths() const { return std::vector<uint64_t>(chrLength.begin(), chrLength.begin() + view.nChrReal); }
 };
 
 // ---- Parameters: defaults of source/parametersDefault + command-line subset ----
@@ -455,18 +458,43 @@ int chimAlignScore(const staramd_params &D, const GenomeIndex &gi, const uint8_t
 
 // signal.cpp: coverage tracks from BAM records in coordinate order; error text or ""
 std::string writeSignal(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength, const std::string &sigFileName, const std::vector<const char *> &recs);
-// the same files from the runs of include/star_amd_signal.h (--gpuSignal Device): res is a staramd_signal_result
-std::string signalFromRuns(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength, const std::string &sigFileName, const void *res);
-// the functions behind --gpuSignal Device (sah_set_signal_device; nullptr while none is installed) and the parameters they take: a staramd_signal_params in
-// `abi`, whose arrays are this object's
+// the same files from the runs of include/star_amd_signal.h (--gpuSignal Device)
+std::string signalFromRuns(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength, const std::string &sigFileName, const staramd_signal_result &R);
+// the functions behind --gpuSignal Device (sah_set_signal_device; nullptr while none is installed) and the parameters they take: `abi`, with this object's arrays
 void setSignalDeviceFns(const ::sah_signal_fns *fns);
 const ::sah_signal_fns *signalDeviceFns();
 inline constexpr const char *SIGNAL_DEVICE_MISSING = "EXITING because of fatal PARAMETERS error: --gpuSignal Device, but no device signal functions are installed (sah_set_signal_device)";
 struct SignalDeviceParams {
-    std::vector<uint32_t> len; std::vector<uint8_t> wanted; alignas(8) unsigned char abi[48];
+    std::vector<uint32_t> len; std::vector<uint8_t> wanted; staramd_signal_params abi;
     void set(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength);
 };
 std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, const std::string &sigFileName);   // --runMode inputAlignmentsFromBAM
+
+// ---- bam_sorted.cpp: Aligned.sortedByCoord.out.bam, and what the end of a run shares with it
+// one late line appended to Log.out or Log.progress.out (their start is written by Runner::init; the reference's log is not reproduced)
+void appendLog(const std::string &path, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+// what a run ends with when a call of an installed device library fails: flag = "--gpuBAMsort" or "--gpuSignal", text = the library's last_error()
+inline std::string deviceError(const char *flag, const char *text) { return std::string("EXITING because of fatal ERROR: ") + flag + " Device: " + text; }
+// --gpuBAMsort Device: the sorter of include/star_amd_bamsort.h, installed by the driver (sah_set_bamsort_device); process-wide, like the BGZF hook
+void setBamsortDevice(const ::sah_bamsort_fns *fns, staramd_bamsort *sorter);
+bool bamsortDeviceInstalled();
+extern const char *const BAMSORT_DEVICE_MISSING;
+// The one owner of Aligned.sortedByCoord.out.bam (BAMbinSortByCoordinate.cpp, BAMbinSortUnmapped.cpp): mapped records by (refID << 32 | pos, read order,
+// order of production), then the unmapped ones in read order.  The reference sorts genomic bins from temporary files; here the records of the run are
+// held until its end -- in host memory, or (--gpuBAMsort Device) in the installed sorter for as long as its budget takes them.
+struct CoordSortedBam {
+    // the keys and records of one range of a batch (the keys' chunk is set here); `raw` is moved from unless the unsorted file is written too.  Error text or ""
+    std::string take(const RunParams &P, std::vector<BamKey> &keys, std::string &raw);
+    // the end of the run: the file, the tracks of --outWigType from the sorted records, the late lines of Log.out.  header: the BAM header, uncompressed
+    std::string write(const RunParams &P, const GenomeIndex &gi, const std::string &header);
+    void abandon(const RunParams &P);           // the run ends without write(): the process-wide sorter is left empty
+    std::vector<std::string> chunks; std::vector<BamKey> keys;      // every record, until write()
+    // --gpuBAMsort Device: the records are in the sorter, append by append; chunks has an empty entry per append, so that BamKey::chunk is the append's number
+    std::vector<uint64_t> appendBytes; bool spilled = false; uint64_t sortCounts[2] = {0, 0}, appendsTaken = 0;
+    uint64_t signalCounts[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // sah_signal_counts
+    bool onDevice(const RunParams &P) const { return P.gpuBAMsortDevice && !spilled; }
+    std::string spill(const RunParams &P);      // the sorter's budget is used up: every append comes back into its entry of chunks, the sorter is emptied
+};
 
 // ---- post-map: multMapSelect, mappedFilter, outputAlignments ----
 class PostMap {

@@ -7,17 +7,14 @@
 // In this file: BatchSet (a batch with its merged mates and WASP reads: the main batch and every slot), EmitRange (everything one range of a batch
 // produces), SamWriter (the writer thread of Aligned.out.sam / .bam and its two sets of ranges), Runner (the run: init, the batch operations on a
 // BatchSet, emitBatch = planEmit / drawRandomOrder / formatRange / compressOnDevice / foldRanges, the phase changes, finish), then the C interface,
-// whose batch operations forward to Runner with the set and the error string of the calling stage.
+// whose batch operations forward to Runner with the set and the error string of the calling stage.  The sorted BAM is CoordSortedBam's (bam_sorted.cpp).
 #include "host.h"
 #include <unistd.h>
 #include <fcntl.h>
 #include <atomic>
 #include <sys/stat.h>
 #include <cerrno>
-#include "../../../include/star_amd_host.h"
-#include "../../../include/star_amd_signal.h"
 #include <cstring>
-#include <cstddef>
 #include <algorithm>
 #include <ctime>
 #include <memory>
@@ -31,13 +28,6 @@
 #include <sys/mman.h>
 
 namespace staramd {
-
-// --gpuBAMsort Device: the sorter of include/star_amd_bamsort.h, installed by the driver (sah_set_bamsort_device); process-wide, like the BGZF hook
-static sah_bamsort_fns g_bamsortFns = {nullptr, nullptr, nullptr, nullptr};
-static void *g_bamsortSorter = nullptr;
-static bool bamsortInstalled() { return g_bamsortFns.append && g_bamsortFns.download && g_bamsortFns.finish && g_bamsortFns.last_error; }
-static const char *const BAMSORT_DEVICE_MISSING = "EXITING because of fatal PARAMETERS error: --gpuBAMsort Device, but no device sorter is installed (sah_set_bamsort_device)";
-static_assert(sizeof(BamKey) == 32 && offsetof(BamKey, off) == 16 && offsetof(BamKey, len) == 24, "BamKey is handed to the sorter as staramd_bam_key");
 
 // one batch with what is mapped beside it: the main batch of the one-batch-at-a-time interface (sah_next_batch ...) and every slot of the pipelined one
 // (sah_fill_slot ...) are such a set, and each batch operation has one body that takes the set
@@ -189,11 +179,7 @@ struct Runner {
     TranscriptAnnotation transcripts; FILE *quantOut = nullptr;     // --quantMode TranscriptomeSAM -> Aligned.toTranscriptome.out.bam
     MultOrder multOrder;
     std::mt19937 rngMultOrder; std::uniform_real_distribution<double> rngUniformReal0to1{0.0, 1.0};   // ReadAlign.cpp:11-12 (one stream: iChunk 0)
-    std::vector<std::string> coordChunks; std::vector<BamKey> coordKeys;     // --outSAMtype BAM SortedByCoordinate: every record, until finish()
-    // --gpuBAMsort Device: the records are in the sorter, append by append; coordChunks has an empty entry per append, so that BamKey::chunk is the append's number
-    std::vector<uint64_t> sortAppendBytes; bool sortSpilled = false; uint64_t sortCounts[2] = {0, 0}, sortAppendsTaken = 0;
-    bool sortOnDevice() const { return P.gpuBAMsortDevice && !sortSpilled; }
-    uint64_t signalCounts[8] = {0, 0, 0, 0, 0, 0, 0, 0};       // sah_signal_counts
+    CoordSortedBam sorted;              // --outSAMtype BAM SortedByCoordinate: every record, until finish()
     int wireTable = 0;                                // which junction table sah_sj_export / import / clear address: 0 = sj, 1 = sj1
     OutSJ &wire() { if (wireTable != 1) sjBg.drainInto(sj); return wireTable == 1 ? sj1 : sj; }
     // The output junction table grows by one record per junction per read.  Whenever it passes sjKick records it is handed to a thread that collapses it and folds it
@@ -420,7 +406,7 @@ struct Runner {
         on.randomOrder = P.outMultimapperRandom;
         on.timing = hostTiming;
         if (on.devBam && !bgzfDeviceInstalled()) { error = BGZF_DEVICE_MISSING; return false; }
-        if (on.coordKeys && P.gpuBAMsortDevice && !bamsortInstalled()) { error = BAMSORT_DEVICE_MISSING; return false; }
+        if (on.coordKeys && P.gpuBAMsortDevice && !bamsortDeviceInstalled()) { error = BAMSORT_DEVICE_MISSING; return false; }
         // T contiguous read ranges, formatted by Wk worker threads that take the next range when they are done with one: with as many
         // ranges as threads the section lasts as long as its slowest thread, and on a shared host (the GPU boxes: 16 CPUs of a 256-thread machine) one descheduled
         // thread held the batch for several times the mean (per-thread busy 2.5 - 5.6 ms in a 24 ms section).  Four ranges per thread; gene counting keeps one
@@ -511,20 +497,6 @@ struct Runner {
         error = bgzfCompressDevice(jobs, P.runThreadN);
         if (pl.on.timing) fprintf(stderr, "  emit: BAM records of %zu ranges compressed on the device, %.2f ms\n", jobs.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td0).count());
     }
-    // --gpuBAMsort Device, the sorter's budget is used up: every append so far comes back into its entry of coordChunks, the sorter is emptied
-    bool spillSort() {
-        for (size_t i = 0; i < sortAppendBytes.size(); i++) {
-            coordChunks[i].resize(sortAppendBytes[i]);
-            if (g_bamsortFns.download(g_bamsortSorter, (uint32_t)i, (uint8_t *)&coordChunks[i][0])) { error = std::string("EXITING because of fatal ERROR: --gpuBAMsort Device: ") + g_bamsortFns.last_error(); return false; }
-        }
-        if (g_bamsortFns.finish(g_bamsortSorter, 0, nullptr, nullptr, nullptr)) { error = std::string("EXITING because of fatal ERROR: --gpuBAMsort Device: ") + g_bamsortFns.last_error(); return false; }
-        sortSpilled = true;
-        if (FILE *lo = fopen((P.outFileNamePrefix + "Log.out").c_str(), "ab")) {
-            fprintf(lo, "--gpuBAMsort Device: the records no longer fit the sorter's budget of device memory after %zu appends; they were brought back and the coordinate sort runs on the host\n", sortAppendBytes.size());
-            fclose(lo);
-        }
-        return true;
-    }
     // step 5, serial and in range order: the ranges into the run's tables and side files
     bool foldRanges(const EmitPlan &pl, std::chrono::steady_clock::time_point te2) {
         const EmitOutputs &on = pl.on;
@@ -541,20 +513,8 @@ struct Runner {
         if (on.chimSam) for (uint32_t t = 0; t < T; t++) if (!R[t].chimSam.empty()) fwrite(R[t].chimSam.data(), 1, R[t].chimSam.size(), chimSamOut);
         if (on.unmapped) for (uint32_t t = 0; t < T; t++) for (uint32_t m = 0; m < P.dev.readNmates; m++)
             if (!R[t].unmapped[m].empty() && unmappedOut[m]) fwrite(R[t].unmapped[m].data(), 1, R[t].unmapped[m].size(), unmappedOut[m]);
-        if (on.coordKeys)                                           // keep the records for the coordinate sort at the end of the run (in memory)
-            for (uint32_t t = 0; t < T; t++) {
-                if (R[t].keys.empty()) continue;
-                uint32_t chunk = (uint32_t)coordChunks.size();
-                for (BamKey &k : R[t].keys) k.chunk = chunk;
-                if (sortOnDevice()) {                                // the records into device memory, only the keys stay here
-                    const int rc = g_bamsortFns.append(g_bamsortSorter, (const uint8_t *)R[t].raw.data(), R[t].raw.size(), R[t].keys.data(), (uint32_t)R[t].keys.size());
-                    if (rc < 0) { error = std::string("EXITING because of fatal ERROR: --gpuBAMsort Device: ") + g_bamsortFns.last_error(); return false; }
-                    if (rc == 0) { coordKeys.insert(coordKeys.end(), R[t].keys.begin(), R[t].keys.end()); coordChunks.emplace_back(); sortAppendBytes.push_back(R[t].raw.size()); sortAppendsTaken++; continue; }
-                    if (!spillSort()) return false;                 // it took nothing: this range and the rest of the run go the Host way
-                }
-                coordKeys.insert(coordKeys.end(), R[t].keys.begin(), R[t].keys.end());
-                coordChunks.emplace_back(P.outBAMunsorted ? R[t].raw : std::move(R[t].raw));
-            }
+        if (on.coordKeys)                                           // keep the records for the coordinate sort at the end of the run
+            for (uint32_t t = 0; t < T; t++) { error = sorted.take(P, R[t].keys, R[t].raw); if (!error.empty()) return false; }
         if (on.stage1) {
             for (uint32_t t = 0; t < T; t++) {
                 sj1.mergeFrom(R[t].sj1);
@@ -602,98 +562,6 @@ struct Runner {
         if (!error.empty() || !foldRanges(pl, te2)) return false;
         if (pl.on.timing) fprintf(stderr, "  emit: before the threads %.2f ms, threads %.2f ms, tail %.2f ms\n", ms(te0, te1) + msBefore, ms(te1, te2) - msBefore, ms(te2, Clock::now()));
         return true;
-    }
-    // Aligned.sortedByCoord.out.bam (BAMbinSortByCoordinate.cpp, BAMbinSortUnmapped.cpp): mapped records by (refID << 32 | pos, read order,
-    // order of production), then the unmapped ones in read order.  The reference sorts genomic bins from temporary files; here all
-    // records of the run are held in memory, ordered once and compressed on the host threads, slice by slice.
-    std::string writeSortedBam() {
-        std::string path = P.outFileNamePrefix + "Aligned.sortedByCoord.out.bam";
-        const bool toStdout = P.outStd == "BAM_SortedByCoordinate";
-        FILE *f = toStdout ? stdout : fopen(path.c_str(), "wb");
-        if (!f) return "EXITING because of fatal ERROR: could not create output file " + path;
-        std::string h;
-        if (!bgzfCompress(post->bamHeader(true), P.outBAMcompression, h)) { if (!toStdout) fclose(f); return "EXITING because of fatal ERROR: BGZF compression failed"; }
-        fwrite(h.data(), 1, h.size(), f);
-        if (sortOnDevice()) {                                       // --gpuBAMsort Device: ordered, laid out and deflated where the records are; the members come back in order
-            if (!bamsortInstalled()) { if (!toStdout) fclose(f); return BAMSORT_DEVICE_MISSING; }
-            int (*put)(void *, const uint8_t *, uint64_t) = [](void *u, const uint8_t *b, uint64_t n) -> int { return fwrite(b, 1, n, (FILE *)u) == n ? 0 : 1; };
-            uint64_t st[8] = {0};
-            // --gpuSignal Device: the same finish, which also computes the tracks where the records lie, after the order is known; they are written once the BAM is
-            const sah_signal_fns *sig = P.wig.yes && P.gpuSignalDevice ? signalDeviceFns() : nullptr;
-            if (P.wig.yes && P.gpuSignalDevice && !sig) { if (!toStdout) fclose(f); return SIGNAL_DEVICE_MISSING; }
-            const std::vector<std::string> chrName(gi.chrName.begin(), gi.chrName.begin() + gi.view.nChrReal);
-            const std::vector<uint64_t> chrLength(gi.chrLength.begin(), gi.chrLength.begin() + gi.view.nChrReal);
-            SignalDeviceParams sp; staramd_signal_result sres; memset(&sres, 0, sizeof(sres));
-            if (sig) sp.set(P, chrName, chrLength);
-            const int rc = sig ? sig->finish_signal(g_bamsortSorter, P.outBAMcompression, put, f, st, sp.abi, &sres) : g_bamsortFns.finish(g_bamsortSorter, P.outBAMcompression, put, f, st);
-            std::string e; bgzfEof(e); fwrite(e.data(), 1, e.size(), f);
-            if (toStdout) fflush(stdout); else fclose(f);
-            const size_t appends = sortAppendBytes.size();
-            coordChunks.clear(); coordKeys.clear(); sortAppendBytes.clear();
-            if (rc) return sig ? std::string("EXITING because of fatal ERROR: --gpuSignal Device: ") + sig->last_error() : std::string("EXITING because of fatal ERROR: --gpuBAMsort Device: ") + g_bamsortFns.last_error();
-            sortCounts[0] = st[0]; sortCounts[1] = st[1];
-            std::string werr;
-            if (sig) {
-                const auto t0 = std::chrono::steady_clock::now();
-                werr = signalFromRuns(P, chrName, chrLength, P.outFileNamePrefix + "Signal", &sres);
-                const uint64_t nsDev = sres.stats[4] + sres.stats[5] + sres.stats[6] + sres.stats[7];
-                signalCounts[0] = 1; signalCounts[1] = sres.stats[0]; signalCounts[2] = sres.stats[1]; signalCounts[3] = sres.stats[3];
-                signalCounts[4] = nsDev + (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-                signalCounts[5] = sres.stats[4]; signalCounts[6] = sres.stats[5]; signalCounts[7] = sres.stats[6];
-                if (getenv("STARAMD_HOST_TIMING")) fprintf(stderr, "  signal stage (device): %.2f ms, of which on the device %.2f ms; %llu bytes of runs\n", signalCounts[4] / 1e6, nsDev / 1e6, (unsigned long long)sres.stats[3]);
-            }
-            if (FILE *lo = fopen((P.outFileNamePrefix + "Log.out").c_str(), "ab")) {
-                fprintf(lo, "--gpuBAMsort Device: %llu records, %llu bytes of %zu appends ordered on the device\n", (unsigned long long)st[0], (unsigned long long)st[1], appends);
-                if (sig) fprintf(lo, "--gpuSignal Device: %llu records, %llu spans in %llu tiles, %llu bytes of runs from the device\n", (unsigned long long)sres.stats[0], (unsigned long long)sres.stats[1], (unsigned long long)sres.stats[2], (unsigned long long)sres.stats[3]);
-                fclose(lo);
-            }
-            if (sig) sig->free_result(&sres);
-            return werr;
-        }
-        std::vector<uint64_t> ord(coordKeys.size());
-        for (uint64_t i = 0; i < ord.size(); i++) ord[i] = i;
-        const std::vector<BamKey> &K = coordKeys;
-        std::sort(ord.begin(), ord.end(), [&K](uint64_t a, uint64_t b) { return K[a].g != K[b].g ? K[a].g < K[b].g : K[a].r != K[b].r ? K[a].r < K[b].r : a < b; });
-        const uint64_t n = ord.size();
-        const uint64_t T = (uint64_t)std::max(1, std::min(P.runThreadN, 64));
-        const uint64_t per = std::max<uint64_t>(4096, (n + 4 * T - 1) / (4 * T));          // records per slice; slices are written in order
-        bool failed = false;
-        const bool dev = P.gpuBAMdevice;                          // --gpuBAMcompression Device: the slices of one round in one hook call
-        if (dev && n > 0 && !bgzfDeviceInstalled()) { if (!toStdout) fclose(f); return BGZF_DEVICE_MISSING; }
-        std::string devErr;
-        for (uint64_t base = 0; base < n && !failed; base += per * T) {
-            std::vector<std::string> outS(T), raws(dev ? T : 0);
-            onThreads(T, CPU_NONE, [&](size_t t) {
-                uint64_t lo = std::min(n, base + t * per), hi = std::min(n, lo + per);
-                std::string raw;
-                for (uint64_t i = lo; i < hi; i++) { const BamKey &k = K[ord[i]]; raw.append(coordChunks[k.chunk], k.off, k.len); }
-                if (dev) raws[t].swap(raw);
-                else if (!bgzfCompress(raw, P.outBAMcompression, outS[t])) failed = true;
-            });
-            if (dev) {
-                std::vector<BgzfJob> jobs;
-                for (uint64_t t = 0; t < T; t++) jobs.push_back({&raws[t], &outS[t], P.outBAMcompression});
-                devErr = bgzfCompressDevice(jobs, P.runThreadN);
-                if (!devErr.empty()) { failed = true; break; }
-            }
-            for (uint64_t t = 0; t < T; t++) if (!outS[t].empty() && fwrite(outS[t].data(), 1, outS[t].size(), f) != outS[t].size()) failed = true;
-        }
-        std::string e; bgzfEof(e); fwrite(e.data(), 1, e.size(), f);
-        if (toStdout) fflush(stdout); else fclose(f);
-        if (P.wig.yes && !failed) {                                 // STAR.cpp:275-283: signal tracks from the sorted alignments
-            std::vector<const char *> recs(n);
-            for (uint64_t i = 0; i < n; i++) { const BamKey &k = K[ord[i]]; recs[i] = coordChunks[k.chunk].data() + k.off; }
-            if (P.gpuSignalDevice)                                  // (the run spilled: its records are here, not on the device)
-                if (FILE *lo = fopen((P.outFileNamePrefix + "Log.out").c_str(), "ab")) { fprintf(lo, "--gpuSignal Device: the sorted records are on the host; the signal tracks are computed on the host\n"); fclose(lo); }
-            const auto t0 = std::chrono::steady_clock::now();
-            std::string werr = writeSignal(P, std::vector<std::string>(gi.chrName.begin(), gi.chrName.begin() + gi.view.nChrReal), std::vector<uint64_t>(gi.chrLength.begin(), gi.chrLength.begin() + gi.view.nChrReal), P.outFileNamePrefix + "Signal", recs);
-            signalCounts[1] = n; signalCounts[4] = (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-            if (getenv("STARAMD_HOST_TIMING")) fprintf(stderr, "  signal stage (host): %.2f ms\n", signalCounts[4] / 1e6);
-            if (!werr.empty()) return werr;
-        }
-        coordChunks.clear(); coordKeys.clear();
-        if (!devErr.empty()) return devErr;
-        return failed ? "EXITING because of fatal ERROR: could not write " + path : "";
     }
     // end of the 1st pass (twoPassRunPass1.cpp:75-96): junctions + Log.final.out of the pass into _STARpass1/, insertion of the
     // junctions into the index, reads rewound.  The caller then re-uploads the index (staramd_update_index).
@@ -765,18 +633,18 @@ struct Runner {
             if (samOut == stdout) fflush(stdout); else fclose(samOut);
             samOut = nullptr;
         }
-        if (P.outBAMcoord && !P.outSAMnone) { error = writeSortedBam(); if (!error.empty()) return false; }
+        if (P.outBAMcoord && !P.outSAMnone) { error = sorted.write(P, gi, post->bamHeader(true)); if (!error.empty()) return false; }
         if (sjThread.joinable()) sjThread.join();
         error = sjError;
         if (!error.empty()) return false;
         stats.reportFinal(P.outFileNamePrefix + "Log.final.out");
-        for (const char *f : {"Log.out", "Log.progress.out"}) { FILE *l = fopen((P.outFileNamePrefix + f).c_str(), "ab"); if (l) { fputs("ALL DONE!\n", l); fclose(l); } }
+        for (const char *f : {"Log.out", "Log.progress.out"}) appendLog(P.outFileNamePrefix + f, "ALL DONE!\n");
         if (P.quantGeneCounts) { error = geneCounts.write(P.outFileNamePrefix + "ReadsPerGene.out.tab", genes, stats); if (!error.empty()) return false; }
         return true;
     }
     ~Runner() {
         writer.stop();
-        if (sortOnDevice() && !sortAppendBytes.empty() && bamsortInstalled()) (void)g_bamsortFns.finish(g_bamsortSorter, 0, nullptr, nullptr, nullptr);      // (a run that ended early leaves the process-wide sorter empty)
+        sorted.abandon(P);      // (a run that ended early leaves the process-wide sorter empty)
         if (getenv("STARAMD_HOST_TIMING")) fprintf(stderr, "  host stages, whole run: writer %.3f s, emit: wait for a text buffer set %.3f s, format on threads %.3f s, serial tail %.3f s\n", writer.seconds, tEmitWaitSet, tEmitFormat, tEmitTail); if (samOut && samOut != stdout) fclose(samOut); if (quantOut == stdout) quantOut = nullptr; for (FILE *u : unmappedOut) if (u) fclose(u); if (chimOut) fclose(chimOut); if (quantOut) fclose(quantOut); }
 };
 
@@ -842,23 +710,20 @@ int sah_generate_finish(void *h, uint64_t nSA, uint64_t nSAbyte, uint64_t nSAiby
 int sah_tool_done(void *h) { return ((Runner *)h)->toolDone ? 1 : 0; }     // 1: the run was a tool mode (--runMode inputAlignmentsFromBAM) and is finished
 int sah_device(void *h) { return ((Runner *)h)->P.gpuDevice; }
 int sah_bgzf_on_device(void *h) { return ((Runner *)h)->P.gpuBAMdevice ? 1 : 0; }
-void sah_set_bamsort_device(const sah_bamsort_fns *fns, void *sorter) {
-    if (fns) staramd::g_bamsortFns = *fns; else staramd::g_bamsortFns = {nullptr, nullptr, nullptr, nullptr};
-    staramd::g_bamsortSorter = fns ? sorter : nullptr;
-}
+void sah_set_bamsort_device(const sah_bamsort_fns *fns, staramd_bamsort *sorter) { staramd::setBamsortDevice(fns, sorter); }
 void sah_set_signal_device(const sah_signal_fns *fns) { staramd::setSignalDeviceFns(fns); }
 int sah_signal_on_device(void *h) { return ((Runner *)h)->P.gpuSignalDevice ? 1 : 0; }
-void sah_signal_counts(void *h, uint64_t out[8]) { for (int i = 0; i < 8; i++) out[i] = ((Runner *)h)->signalCounts[i]; }
+void sah_signal_counts(void *h, uint64_t out[8]) { for (int i = 0; i < 8; i++) out[i] = ((Runner *)h)->sorted.signalCounts[i]; }
 int sah_signal_files_from_runs(int argc, char **argv, int nChr, const char *const *chrName, const uint64_t *chrLength, const void *result, char *errbuf, int errlen) {
     staramd::RunParams P;
     std::string e = P.parse(argc, argv);
-    if (e.empty()) e = staramd::signalFromRuns(P, std::vector<std::string>(chrName, chrName + nChr), std::vector<uint64_t>(chrLength, chrLength + nChr), P.outFileNamePrefix + "Signal", result);
+    if (e.empty()) e = staramd::signalFromRuns(P, std::vector<std::string>(chrName, chrName + nChr), std::vector<uint64_t>(chrLength, chrLength + nChr), P.outFileNamePrefix + "Signal", *(const staramd_signal_result *)result);
     if (errbuf && errlen > 0) { strncpy(errbuf, e.c_str(), errlen - 1); errbuf[errlen - 1] = 0; }
     return e.empty() ? 0 : -1;
 }
 int sah_bamsort_on_device(void *h) { return ((Runner *)h)->P.gpuBAMsortDevice ? 1 : 0; }
 uint64_t sah_bamsort_budget(void *h) { return ((Runner *)h)->P.gpuBAMsortHBM; }
-void sah_bam_sort_counts(void *h, uint64_t out[4]) { Runner *r = (Runner *)h; out[0] = r->sortCounts[0]; out[1] = r->sortCounts[1]; out[2] = r->sortAppendsTaken; out[3] = r->sortSpilled ? 1 : 0; }
+void sah_bam_sort_counts(void *h, uint64_t out[4]) { const staramd::CoordSortedBam &s = ((Runner *)h)->sorted; out[0] = s.sortCounts[0]; out[1] = s.sortCounts[1]; out[2] = s.appendsTaken; out[3] = s.spilled ? 1 : 0; }
 double sah_genome_load_seconds(void *h) { return ((Runner *)h)->gi.loadSeconds; }
 void sah_cpu_add(int stage, uint64_t ns) { staramd::cpuAdd(stage, ns); }
 void sah_cpu_seconds(double out[8], int reset) { for (int i = 0; i < staramd::CPU_NSTAGE; i++) out[i] = (double)staramd::cpuTake(i, reset != 0) * 1e-9; }

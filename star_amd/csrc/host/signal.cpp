@@ -3,8 +3,6 @@
 //   signalFromBAM     source/signalFromBAM.cpp:5-209   (the reference re-reads its sorted BAM; here the sorted records are still in memory)
 // --gpuSignal Device: the values are computed on the MI355X (include/star_amd_signal.h) and come back as runs; signalFromRuns writes the same files from them.
 #include "host.h"
-#include "../../../include/star_amd_host.h"
-#include "../../../include/star_amd_signal.h"
 #include <cstring>
 #include <cstdio>
 #include <zlib.h>
@@ -144,16 +142,12 @@ void SignalDeviceParams::set(const RunParams &P, const std::vector<std::string> 
         len[i] = (uint32_t)chrLength[i];
         wanted[i] = W.referencesPrefix.empty() || chrName[i].compare(0, W.referencesPrefix.size(), W.referencesPrefix) == 0;
     }
-    static_assert(sizeof(staramd_signal_params) <= sizeof(abi), "SignalDeviceParams::abi holds a staramd_signal_params");
-    staramd_signal_params sp; memset(&sp, 0, sizeof(sp));
-    sp.type = W.type; sp.strand = W.strand ? 1 : 0; sp.nChr = (uint32_t)chrName.size(); sp.wantNorm = W.norm == 1; sp.chrLength = len.data(); sp.wanted = wanted.data();
-    memcpy(abi, &sp, sizeof(sp));
+    abi = {W.type, W.strand ? 1 : 0, (uint32_t)chrName.size(), W.norm == 1, len.data(), wanted.data()};
 }
 
 // The files of writeSignal from runs: same names, same formats, same normFactor arithmetic.  A run is joined with the next of its track when they touch and
 // hold the same value (a tile boundary of the device must not show in a bedGraph line); wiggle prints every position of a run
-std::string signalFromRuns(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength, const std::string &sigFileName, const void *resv) {
-    const staramd_signal_result &R = *(const staramd_signal_result *)resv;
+std::string signalFromRuns(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength, const std::string &sigFileName, const staramd_signal_result &R) {
     const WigParams &W = P.wig;
     double nMult = 0, nUniq = 0;
     if (W.norm == 1 && R.norm) for (uint64_t i = 0; i < R.nRecords; i++) { const uint32_t nh = R.norm[i]; if (nh == 1) ++nUniq; else if (nh > 1) nMult += 1.0 / nh; }      // in the records' order, as writeSignal
@@ -250,8 +244,8 @@ std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, co
         for (size_t i = 0; i < recs.size(); i++) offsets[i] = (uint64_t)(recs[i] - d.data());
         SignalDeviceParams sp; sp.set(P, chrName, chrLength);
         staramd_signal_result res;
-        if (fns->host_records(P.gpuDevice, sp.abi, (const uint8_t *)d.data(), d.size(), offsets.data(), offsets.size(), &res)) return std::string("EXITING because of fatal ERROR: --gpuSignal Device: ") + fns->last_error();
-        std::string e = signalFromRuns(P, chrName, chrLength, sigFileName, &res);
+        if (fns->host_records(P.gpuDevice, &sp.abi, (const uint8_t *)d.data(), d.size(), offsets.data(), offsets.size(), &res)) return deviceError("--gpuSignal", fns->last_error());
+        std::string e = signalFromRuns(P, chrName, chrLength, sigFileName, res);
         fns->free_result(&res);
         return e;
     }

@@ -3,15 +3,15 @@ output is the records in the order of the host comparator (g, r, order of append
 (same kernel, same block cut: one segment, every member but the last 0xff00 bytes); budget, download and the front end (capi.HostRun with the emulated
 sorter behind sah_set_bamsort_device: Device against Host, --runThreadN 1 against 3, the spill to the host path, the flags).
 The GPU tests (tests/test_gpu_bamsort.py) hold the shipped library to the bytes made here, vector by vector."""
+import ctypes as C
 import os
 import random
 import struct
-import subprocess
 import tempfile
 
 import pytest
 
-from util import ROOT, _map, bam_parts, capi, oracle_lib
+from util import _map, bam_parts, capi, emul_units_lib, oracle_lib
 import test_golden
 import test_bgzf_emul as E
 
@@ -19,27 +19,12 @@ IN_MAX = 0xff00
 TILE = 32768                    # output bytes per workgroup of k_bamsort_gather, 127 records per LDS chunk
 UNMAPPED = (1 << 64) - 1
 LEVELS = (0, 1, 6)
-_LIB = {}
 _VEC = {}
 
 
 def emul_lib():
-    """k_bgzf.hip + k_bamsort.hip + the emulator's runtime in a temporary shared library (built once per process; oracle/ is only read)"""
-    if "so" not in _LIB:
-        d = tempfile.mkdtemp(prefix="staramd_bamsort_emul_")
-        cl = os.environ.get("EMUL_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-        hipfl = ["-x", "c++", "-std=c++17", "-O1", "-fPIC", "-Wno-unknown-attributes", "-I", "oracle/wave_emul"]
-        objs = []
-        for src, fl in (("star_amd/csrc/engine/k_bgzf.hip", hipfl), ("star_amd/csrc/engine/k_bamsort.hip", hipfl),
-                        ("oracle/wave_emul/emu.cpp", ["-std=c++17", "-O1", "-fPIC", "-D_GNU_SOURCE"]),
-                        ("oracle/wave_emul/emu_lds.cpp", ["-std=c++17", "-O1", "-fPIC"])):
-            o = os.path.join(d, os.path.basename(src) + ".o")
-            subprocess.check_call([cl] + fl + ["-c", src, "-o", o], cwd=ROOT)
-            objs.append(o)
-        so = os.path.join(d, "libbamsort_emul.so")
-        subprocess.check_call([cl, "-shared", "-fPIC"] + objs + ["-o", so, "-ldl"], cwd=ROOT)
-        _LIB["so"] = so
-    return _LIB["so"]
+    """the library of the emulated device units (util.emul_units_lib: built once per process)"""
+    return emul_units_lib()
 
 
 def _record(r, i, n):
@@ -343,3 +328,76 @@ def test_host_is_the_default(front_end, tmp_path):
     out, c = run_sorted(front_end["info"], str(tmp_path / "plain_"), BOTH + ["--runThreadN", "3"], sorter=False)
     assert c == [0, 0, 0, 0]
     assert _after_header(out + SORTED) == _after_header(front_end["Host"][0] + SORTED) and E.same_bam(out + SORTED, front_end["Host"][0] + SORTED)
+
+
+# ---- the front end's handling of the sorter, with a sorter made of Python callbacks ------------------------------------------------------------
+
+class FakeSorter:
+    """a sah_bamsort_fns of Python callbacks for HostRun.set_bamsort_device: append answers append_rc(number of the call), download and finish (with a
+    sink) answer the given codes; the calls are counted, and for every finish whether its sink was null"""
+    TEXT = "the fake sorter's own words"
+
+    def __init__(self, append_rc=lambda k: 0, download_rc=0, finish_rc=0):
+        self.appends, self.downloads, self.finish_sink_null = 0, 0, []
+        self._text = C.create_string_buffer(self.TEXT.encode())
+
+        def append(sorter, records, n_bytes, keys, n):
+            self.appends += 1
+            return append_rc(self.appends)
+
+        def download(sorter, i_append, records):
+            self.downloads += 1
+            return download_rc
+
+        def finish(sorter, level, sink, user, stats):
+            self.finish_sink_null.append(not sink)
+            return finish_rc if sink else 0
+
+        self._cb = [C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32)(append),
+                    C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.c_void_p)(download),
+                    C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p)(finish),
+                    C.CFUNCTYPE(C.c_void_p)(lambda: C.addressof(self._text))]
+
+    def fns(self):
+        return capi.BamSortFns(*[C.cast(f, C.c_void_p) for f in self._cb]), None
+
+
+def run_with_fake(prefix, fake, finish=True):
+    """the tiny data set with --gpuBAMsort Device and `fake` installed, in batches of 300 reads; finish=False: destroyed after the last batch, without sah_finish"""
+    run = capi.HostRun(_argv(test_golden._tiny_info(), prefix, ["--outSAMtype", "BAM", "SortedByCoordinate", "--gpuBAMsort", "Device"]))
+    eng = oracle_lib.Oracle(run.genome, run.params)
+    try:
+        run.set_bamsort_device(fake)
+        while True:
+            b = run.next_batch(300)
+            if b is None:
+                break
+            run.emit(_map(eng, b).res)
+        assert run.next_phase() == 0
+        if finish:
+            run.finish()
+    finally:
+        eng.close()
+        run.close()
+
+
+@pytest.mark.parametrize("case", ["append", "download_in_spill", "finish"])
+def test_sorter_errors_end_the_run_with_the_sorters_text(case, tmp_path, built):
+    fake = {"append": lambda: FakeSorter(append_rc=lambda k: -1),
+            "download_in_spill": lambda: FakeSorter(append_rc=lambda k: 1 if k == 2 else 0, download_rc=-1),
+            "finish": lambda: FakeSorter(finish_rc=-1)}[case]()
+    with pytest.raises(RuntimeError) as e:
+        run_with_fake(str(tmp_path / "a_"), fake)
+    assert str(e.value) == "EXITING because of fatal ERROR: --gpuBAMsort Device: " + FakeSorter.TEXT
+    if case == "append":
+        assert fake.appends == 1 and fake.downloads == 0 and fake.finish_sink_null == []
+    elif case == "download_in_spill":
+        assert fake.appends == 2 and fake.downloads == 1 and fake.finish_sink_null == [True]      # (the run's end leaves the sorter emptied)
+    else:
+        assert fake.appends >= 2 and fake.finish_sink_null == [False]
+
+
+def test_run_destroyed_after_appends_empties_the_sorter(tmp_path, built):
+    fake = FakeSorter()
+    run_with_fake(str(tmp_path / "a_"), fake, finish=False)
+    assert fake.appends >= 2 and fake.finish_sink_null == [True]

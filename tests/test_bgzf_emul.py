@@ -9,40 +9,24 @@ import math
 import os
 import random
 import struct
-import subprocess
-import tempfile
 import threading
 import time
 import zlib
 
 import pytest
 
-from util import ROOT, _map, bam_parts, capi, oracle_lib, prepare, refstar, run_with_engine
+from util import _map, bam_parts, capi, emul_units_lib, oracle_lib, prepare, refstar, run_with_engine
 import test_golden
 
 IN_MAX = 0xff00
 LEVELS = (0, 1, 2, 6, 9, -1)       # one level per row of the kernel's table and both ends: 3 is 2 again; 4, 5, 7, 8, 9 and -1 are 6 again
 EOF_MARK = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
-_LIB = {}
 _EDGE = {}
 
 
 def emul_lib():
-    """k_bgzf.hip + the emulator's runtime in a temporary shared library (built once per process; oracle/ is only read)"""
-    if "so" not in _LIB:
-        d = tempfile.mkdtemp(prefix="staramd_bgzf_emul_")
-        cl = os.environ.get("EMUL_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-        objs = []
-        for src, fl in (("star_amd/csrc/engine/k_bgzf.hip", ["-x", "c++", "-std=c++17", "-O1", "-fPIC", "-Wno-unknown-attributes", "-I", "oracle/wave_emul"]),
-                        ("oracle/wave_emul/emu.cpp", ["-std=c++17", "-O1", "-fPIC", "-D_GNU_SOURCE"]),
-                        ("oracle/wave_emul/emu_lds.cpp", ["-std=c++17", "-O1", "-fPIC"])):
-            o = os.path.join(d, os.path.basename(src) + ".o")
-            subprocess.check_call([cl] + fl + ["-c", src, "-o", o], cwd=ROOT)
-            objs.append(o)
-        so = os.path.join(d, "libbgzf_emul.so")
-        subprocess.check_call([cl, "-shared", "-fPIC"] + objs + ["-o", so, "-ldl"], cwd=ROOT)
-        _LIB["so"] = so
-    return _LIB["so"]
+    """the library of the emulated device units (util.emul_units_lib: built once per process)"""
+    return emul_units_lib()
 
 
 def synthetic_vectors():

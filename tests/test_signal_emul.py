@@ -13,7 +13,7 @@ import zlib
 
 import pytest
 
-from util import ROOT, capi, refstar
+from util import capi, emul_units_lib, refstar
 import test_bamsort_emul as S
 
 T = 1024                        # positions per tile of k_signal_tiles
@@ -22,26 +22,11 @@ CHROMS = [("chrA", 700000), ("chrB", 3000), ("chrC", 5000), ("other1", 2000)]
 CHR_NAMES = [c for c, _ in CHROMS]
 CHR_LEN = [n for _, n in CHROMS]
 BUG = "BUG: alignment extends past chromosome in the signal output"
-_LIB = {}
 
 
 def emul_lib():
-    """k_bgzf.hip + k_bamsort.hip + k_signal.hip + the emulator's runtime in a temporary shared library (built once per process; oracle/ is only read)"""
-    if "so" not in _LIB:
-        d = tempfile.mkdtemp(prefix="staramd_signal_emul_")
-        cl = os.environ.get("EMUL_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-        hipfl = ["-x", "c++", "-std=c++17", "-O1", "-fPIC", "-Wno-unknown-attributes", "-I", "oracle/wave_emul"]
-        objs = []
-        for src, fl in (("star_amd/csrc/engine/k_bgzf.hip", hipfl), ("star_amd/csrc/engine/k_bamsort.hip", hipfl), ("star_amd/csrc/engine/k_signal.hip", hipfl),
-                        ("oracle/wave_emul/emu.cpp", ["-std=c++17", "-O1", "-fPIC", "-D_GNU_SOURCE"]),
-                        ("oracle/wave_emul/emu_lds.cpp", ["-std=c++17", "-O1", "-fPIC"])):
-            o = os.path.join(d, os.path.basename(src) + ".o")
-            subprocess.check_call([cl] + fl + ["-c", src, "-o", o], cwd=ROOT)
-            objs.append(o)
-        so = os.path.join(d, "libsignal_emul.so")
-        subprocess.check_call([cl, "-shared", "-fPIC"] + objs + ["-o", so, "-ldl"], cwd=ROOT)
-        _LIB["so"] = so
-    return _LIB["so"]
+    """the library of the emulated device units (util.emul_units_lib: built once per process)"""
+    return emul_units_lib()
 
 
 # ---- fabricated BAM ------------------------------------------------------------------------------------------------------------------------------

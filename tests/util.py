@@ -1,7 +1,9 @@
 """Shared helpers for the parity tests."""
 import os
 import shutil
+import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -44,6 +46,29 @@ DATASETS = {
     "pe150_chim": (dict(seed=5, chr_lengths=(350000, 250000, 200000), n_tr=110, n_reads=3000, read_len=150, paired=True, sub_rate=0.01, chim_rate=0.05),
                    dict(sa_index_nbases=8, use_gtf=True, sjdb_overhang=149), []),
 }
+
+
+_EMUL_UNITS = {}
+
+
+def emul_units_lib():
+    """k_bgzf.hip + k_bamsort.hip + k_signal.hip (the stand-alone device units) + the wave emulator's runtime in a temporary shared library, built
+    once per process; oracle/ is only read.  The emul_lib() of tests/test_bgzf_emul.py, test_bamsort_emul.py and test_signal_emul.py"""
+    if "so" not in _EMUL_UNITS:
+        d = tempfile.mkdtemp(prefix="staramd_units_emul_")
+        cl = os.environ.get("EMUL_CXX", "/opt/rocm/lib/llvm/bin/clang++")
+        hipfl = ["-x", "c++", "-std=c++17", "-O1", "-fPIC", "-Wno-unknown-attributes", "-I", "oracle/wave_emul"]
+        objs = []
+        for src, fl in (("star_amd/csrc/engine/k_bgzf.hip", hipfl), ("star_amd/csrc/engine/k_bamsort.hip", hipfl), ("star_amd/csrc/engine/k_signal.hip", hipfl),
+                        ("oracle/wave_emul/emu.cpp", ["-std=c++17", "-O1", "-fPIC", "-D_GNU_SOURCE"]),
+                        ("oracle/wave_emul/emu_lds.cpp", ["-std=c++17", "-O1", "-fPIC"])):
+            o = os.path.join(d, os.path.basename(src) + ".o")
+            subprocess.check_call([cl] + fl + ["-c", src, "-o", o], cwd=ROOT)
+            objs.append(o)
+        so = os.path.join(d, "libunits_emul.so")
+        subprocess.check_call([cl, "-shared", "-fPIC"] + objs + ["-o", so, "-ldl"], cwd=ROOT)
+        _EMUL_UNITS["so"] = so
+    return _EMUL_UNITS["so"]
 
 
 # non-default alignReads flags, one group per entry: every branch the flags of SURVEY.md 5.6 switch on the hot path and in post-map

@@ -7,7 +7,7 @@ Then the SortedByCoordinate leg of --gpuBAMsort: compression Host + sort Host, c
 and, for the Device sort, the split of staramd_bamsort_finish (its STARAMD_HOST_TIMING line) with the gather kernel's bytes read + written per second.
 With --wig (a --sorted-only form) the leg is that of --gpuSignal: Host sort + host signal and Device sort + --gpuSignal Device, both with --outWigType bedGraph,
 and beside them the same two forms without --outWigType (they run no signal code): finishSeconds, the signal stage's own time on both sides (the
-STARAMD_HOST_TIMING lines of runner.cpp), the device's split per kernel group and the bytes of the runs (k_signal.hip's line).
+STARAMD_HOST_TIMING lines of bam_sorted.cpp), the device's split per kernel group and the bytes of the runs (k_signal.hip's line).
   python tools/bam_device_leg.py [--sorted-only [--wig]] [--sort-repeats N] [--reads N ...bench.py flags] [ENV=V ...]     (GPU box)"""
 import hashlib, json, os, re, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
