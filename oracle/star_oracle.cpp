@@ -851,6 +851,49 @@ struct Oracle {
         return status;
     }
 
+    // the result arrays of one read from its trAll[][] (what staramd_map_batch returns, include/star_amd.h): windows in order, transcripts best first, under
+    // resultSelect != 0 only what multMapSelect can pick.  A member of its own so that oracle/tail_routines_check.cpp can hold k_stitch_finish / k_gather to it
+    // on window lists made by hand; rr.trOffset is the caller's (otr.size() before the call)
+    static void emitRead(const std::vector<std::vector<Tr>> &trAll, int bw, const staramd_params &P, staramd_read_result &rr, std::vector<staramd_transcript> &otr, std::vector<staramd_exon> &oex) {
+        // staramd_params::resultSelect == 1: keep only what multMapSelect can pick (ReadAlign_multMapSelect.cpp:26-44)
+        const bool sel = P.resultSelect != 0 && bw >= 0;
+        const int selMin = sel ? trAll[bw][0].maxScore - P.outFilterMultimapScoreRange : 0;
+        u64 nWout = 0;
+        for (u64 iW = 0; iW < trAll.size(); iW++) {
+            if (sel && trAll[iW][0].maxScore < selMin) continue;     // transcripts of a window are sorted best first
+            if ((int)iW == bw) rr.trBest = (int32_t)(otr.size() - rr.trOffset);
+            for (u64 it = 0; it < trAll[iW].size(); it++) {
+                const Tr &t = trAll[iW][it];
+                if (sel && t.maxScore < selMin) break;
+                staramd_transcript o; memset(&o, 0, sizeof(o));
+                o.iW = (uint32_t)nWout; o.exonOffset = (uint32_t)oex.size(); o.nExons = (uint16_t)t.nExons;
+                o.rStart = (uint16_t)t.rStart; o.rLength = (uint16_t)t.rLength; o.roStart = (uint16_t)t.roStart;
+                o.Str = (uint8_t)trAll[iW][0].Str; o.roStr = (uint8_t)trAll[iW][0].roStr; o.iFrag = (int8_t)t.iFrag; o.sjMotifStrand = t.sjMotifStrand;
+                o.Chr = (uint32_t)trAll[iW][0].Chr; o.gStart = t.gStart; o.gLength = t.gLength; o.maxScore = t.maxScore;
+                o.nMatch = (uint32_t)t.nMatch; o.nMM = (uint32_t)t.nMM; o.mappedLength = (uint32_t)t.mappedLength;
+                o.nGap = (uint32_t)t.nGap; o.lGap = (uint32_t)t.lGap; o.nDel = (uint32_t)t.nDel; o.lDel = (uint32_t)t.lDel; o.nIns = (uint32_t)t.nIns; o.lIns = (uint32_t)t.lIns;
+                o.nUnique = (uint16_t)t.nUnique; o.nAnchor = (uint16_t)t.nAnchor;
+                for (int k = 0; k < 3; k++) o.intronMotifs[k] = (uint16_t)t.intronMotifs[k];
+                for (u64 ie = 0; ie < t.nExons; ie++) {
+                    staramd_exon e; memset(&e, 0, sizeof(e));
+                    e.G = t.ex[ie][EX_G]; e.R = (uint16_t)t.ex[ie][EX_R]; e.L = (uint16_t)t.ex[ie][EX_L];
+                    e.sjA = (int32_t)(i64)t.ex[ie][EX_sjA]; e.iFrag = (uint8_t)t.ex[ie][EX_iFrag];
+                    if (ie + 1 < t.nExons) {
+                        e.canonSJ = (int8_t)t.canonSJ[ie]; e.sjAnnot = t.sjAnnot[ie]; e.sjStr = t.sjStr[ie];
+                        bool sh = t.canonSJ[ie] >= 0;   // shiftSJ is only defined for junctions (not for indels / mate gap)
+                        e.shiftSJ[0] = sh ? (uint16_t)t.shiftSJ[ie][0] : 0; e.shiftSJ[1] = sh ? (uint16_t)t.shiftSJ[ie][1] : 0;
+                    }
+                    oex.push_back(e);
+                }
+                otr.push_back(o);
+            }
+            nWout++;
+        }
+        rr.nW = (uint32_t)nWout;
+        if (rr.nW > 0) rr.status |= STARAMD_ST_MAPPED_WINDOWS;
+        rr.nTr = (uint32_t)(otr.size() - rr.trOffset);
+    }
+
     // ------------------------------------------------------------------ ReadAlign_mapOneRead.cpp:6-118
     void mapOneRead(const uint8_t *read, u64 L, u64 len1, u64 mmMax, staramd_read_result &rr, std::vector<staramd_transcript> &otr, std::vector<staramd_exon> &oex) {
         Lread = L; readLength[0] = len1; readLength[1] = P.readNmates == 2 ? L - len1 - 1 : 0; mmMaxTotal = mmMax;
@@ -902,43 +945,7 @@ struct Oracle {
         else {
             int bw;
             rr.status |= stitchPieces(bw);
-            // staramd_params::resultSelect == 1: keep only what multMapSelect can pick (ReadAlign_multMapSelect.cpp:26-44)
-            const bool sel = P.resultSelect != 0 && bw >= 0;
-            const int selMin = sel ? trAll[bw][0].maxScore - P.outFilterMultimapScoreRange : 0;
-            u64 nWout = 0;
-            for (u64 iW = 0; iW < trAll.size(); iW++) {
-                if (sel && trAll[iW][0].maxScore < selMin) continue;     // transcripts of a window are sorted best first
-                if ((int)iW == bw) rr.trBest = (int32_t)(otr.size() - rr.trOffset);
-                for (u64 it = 0; it < trAll[iW].size(); it++) {
-                    const Tr &t = trAll[iW][it];
-                    if (sel && t.maxScore < selMin) break;
-                    staramd_transcript o; memset(&o, 0, sizeof(o));
-                    o.iW = (uint32_t)nWout; o.exonOffset = (uint32_t)oex.size(); o.nExons = (uint16_t)t.nExons;
-                    o.rStart = (uint16_t)t.rStart; o.rLength = (uint16_t)t.rLength; o.roStart = (uint16_t)t.roStart;
-                    o.Str = (uint8_t)trAll[iW][0].Str; o.roStr = (uint8_t)trAll[iW][0].roStr; o.iFrag = (int8_t)t.iFrag; o.sjMotifStrand = t.sjMotifStrand;
-                    o.Chr = (uint32_t)trAll[iW][0].Chr; o.gStart = t.gStart; o.gLength = t.gLength; o.maxScore = t.maxScore;
-                    o.nMatch = (uint32_t)t.nMatch; o.nMM = (uint32_t)t.nMM; o.mappedLength = (uint32_t)t.mappedLength;
-                    o.nGap = (uint32_t)t.nGap; o.lGap = (uint32_t)t.lGap; o.nDel = (uint32_t)t.nDel; o.lDel = (uint32_t)t.lDel; o.nIns = (uint32_t)t.nIns; o.lIns = (uint32_t)t.lIns;
-                    o.nUnique = (uint16_t)t.nUnique; o.nAnchor = (uint16_t)t.nAnchor;
-                    for (int k = 0; k < 3; k++) o.intronMotifs[k] = (uint16_t)t.intronMotifs[k];
-                    for (u64 ie = 0; ie < t.nExons; ie++) {
-                        staramd_exon e; memset(&e, 0, sizeof(e));
-                        e.G = t.ex[ie][EX_G]; e.R = (uint16_t)t.ex[ie][EX_R]; e.L = (uint16_t)t.ex[ie][EX_L];
-                        e.sjA = (int32_t)(i64)t.ex[ie][EX_sjA]; e.iFrag = (uint8_t)t.ex[ie][EX_iFrag];
-                        if (ie + 1 < t.nExons) {
-                            e.canonSJ = (int8_t)t.canonSJ[ie]; e.sjAnnot = t.sjAnnot[ie]; e.sjStr = t.sjStr[ie];
-                            bool sh = t.canonSJ[ie] >= 0;   // shiftSJ is only defined for junctions (not for indels / mate gap)
-                            e.shiftSJ[0] = sh ? (uint16_t)t.shiftSJ[ie][0] : 0; e.shiftSJ[1] = sh ? (uint16_t)t.shiftSJ[ie][1] : 0;
-                        }
-                        oex.push_back(e);
-                    }
-                    otr.push_back(o);
-                }
-                nWout++;
-            }
-            rr.nW = (uint32_t)nWout;
-            if (rr.nW > 0) rr.status |= STARAMD_ST_MAPPED_WINDOWS;
-            rr.nTr = (uint32_t)(otr.size() - rr.trOffset);
+            emitRead(trAll, bw, P, rr, otr, oex);
             cnt[C_nTrOut] += rr.nTr;
         }
         rr.maxScoreMate[0] = maxScoreMate[0]; rr.maxScoreMate[1] = maxScoreMate[1];

@@ -25,6 +25,8 @@ extern thread_local uint32_t ldsReads[];
 
 static std::mt19937_64 rng(20250117);
 static u32 rnd(u32 n) { return (u32)(rng() % n); }
+#include "cand_log_ref.h"
+static_assert(CAND_NE_MAX == SRS_NE_MAX, "the candidates of cand_log_ref.h fill the record stride of the probes");
 
 // ---- classes -----------------------------------------------------------------------------------------------------------------------------------------------------------
 enum { E_SCAN_LE64, E_SCAN_65_128, E_SCAN_GT128, E_LEN_TRIP1, E_LEN_TRIP2, E_LEN_TRIP3, E_BUDGET_LATE, E_SPACER, E_PAD_LOW, E_PAD_HIGH, E_N_READ, E_N_GENOME, E_TOEND_LEN, E_TOEND_FAIL, E_L_NONPOS, E_MATEGAP,
@@ -343,16 +345,7 @@ static void makeTable(SrsSet &S, u32 N, bool cover, u32 nSample) {
 }
 
 // ---- candidate logs and the sequential list -------------------------------------------------------------------------------------------------------------------------------------
-struct Cand { staramd_transcript t; staramd_exon ex[SRS_NE_MAX]; };
-static Tr asTr(const staramd_exon *ex, u32 ne, u32 mapped) { Tr t; memset(&t, 0, sizeof(t)); t.nExons = ne; t.mappedLength = mapped; for (u32 k = 0; k < ne; k++) { t.ex[k][EX_R] = ex[k].R; t.ex[k][EX_L] = ex[k].L; t.ex[k][EX_G] = ex[k].G; } return t; }
-static void randomBytes(void *p, size_t n) { u8 *b = (u8 *)p; for (size_t i = 0; i < n; i++) b[i] = (u8)rng(); }
-// exons on the diagonals diag[] (G - R): ne sorted pieces of the read [0, span)
-static void layExons(Cand &c, u32 ne, const u64 *diag, u32 nDiag, u32 span) {
-    std::vector<u32> cut; while (cut.size() < 2 * ne) { const u32 p = rnd(span + 1); if (std::find(cut.begin(), cut.end(), p) == cut.end()) cut.push_back(p); } std::sort(cut.begin(), cut.end());
-    u32 mapped = 0;
-    for (u32 k = 0; k < ne; k++) { staramd_exon &e = c.ex[k]; randomBytes(&e, sizeof(e)); e.R = (u16)cut[2 * k]; e.L = (u16)(cut[2 * k + 1] - cut[2 * k]); e.G = diag[rnd(nDiag)] + e.R; e.pad0 = e.pad1 = 0; mapped += e.L; }
-    c.t.nExons = (u16)ne; c.t.mappedLength = mapped;
-}
+// (Cand, asTr, randomBytes, layExons, candLogBytes and the sequential list itself: cand_log_ref.h, shared with oracle/tail_routines_check.cpp)
 static void runLogs(SrsSet &S, u32 nLogs) {
     static const u32 NMAX[7] = {1, 3, 63, 64, 65, 100, 130};
     for (u32 il = 0; il < nLogs; il++) {
@@ -377,47 +370,18 @@ static void runLogs(SrsSet &S, u32 nLogs) {
                 c.t.maxScore = pattern == 3 ? 70 + (i32)rnd(3) : (i32)(b - a) - (i32)rnd(2);
                 if (pattern != 3 && rnd(3)) c.t.maxScore = 80 - (i32)rnd(2) + (i32)(b - a) / 40; }
         }
-        const u64 candOff = S.logPool.size(); std::vector<u32> sizes(nCand);
-        for (u32 k = 0; k < nCand; k++) { const Cand &c = cand[k]; sizes[k] = REC_HDR + 32u * c.t.nExons; const u8 *p = (const u8 *)&c.t; S.logPool.insert(S.logPool.end(), p, p + REC_HDR); p = (const u8 *)c.ex; S.logPool.insert(S.logPool.end(), p, p + 32u * c.t.nExons); }
+        const u64 candOff = S.logPool.size(); candLogBytes(cand, S.logPool);
         // four runs of the log: the product's LDS arena in both forms, the product's large arena in global memory, the wide LDS arena
         for (u32 run = 0; run < 4; run++) {
             SrsLog g; memset(&g, 0, sizeof(g)); g.candOff = candOff; g.nCand = nCand; g.Nmax = Nmax; g.minIn[0] = minIn[0]; g.minIn[1] = minIn[1]; g.range = range; g.chim = chim;
             g.form = run == 0 ? 0u : run == 1 ? 1u : (il + run) & 1u; g.big = run == 2; g.arenaBytes = run < 2 ? 3584u : run == 2 ? 2u * (Nmax + 2u) * (96u + 32u * STARAMD_MAX_N_EXONS) : SRS_ARENA_WIDE;
             nClass[g.form ? R_FORM_WALK : R_FORM_REPLAY]++;
-            // stitchWindowAligns.cpp:232-303 one candidate after the other (the form of star_oracle.cpp:705-723, the maxScoreMate pre-filter as in replayWindow), and the arena's book-keeping
-            std::vector<u32> list; i32 M[2] = {minIn[0], minIn[1]}; u32 top = 0; bool ovf = false;
-            for (u32 k = 0; k < nCand && !ovf; k++) {
-                const Cand &c = cand[k]; const int Score = c.t.maxScore, f = c.t.iFrag; i32 Mf = 0;
-                if (f >= 0) { M[f] = std::max(M[f], Score); Mf = M[f]; }
-                const i32 best = list.empty() ? 0 : cand[list[0]].t.maxScore;
-                if (!(Score + range >= best || chim || (f >= 0 && Score + range >= Mf))) continue;
-                const u32 n0 = (u32)list.size(); if (n0 > 64) { nClass[R_LIST_64]++; if (!g.big) nClass[R_LDS_LIST_64]++; } if (n0 > 128) nClass[R_LIST_128]++;
-                const Tr tn = asTr(c.ex, c.t.nExons, c.t.mappedLength);
-                u32 iTr = 0, orig = 0; bool blocked = false;
-                while (iTr < list.size()) {
-                    const Cand &o = cand[list[iTr]]; const Tr to = asTr(o.ex, o.t.nExons, o.t.mappedLength);
-                    const u64 nOverlap = Oracle::blocksOverlap(tn, to), uNew = tn.mappedLength - nOverlap, uOld = to.mappedLength - nOverlap;
-                    if (uNew == 0 && Score < o.t.maxScore) { blocked = true; if (orig < 64 && n0 > 64) nClass[R_TAIL]++; break; }
-                    else if (uOld == 0) { list.erase(list.begin() + iTr); if (orig >= 64) nClass[R_REMOVE_TRIP2]++; }
-                    else iTr++;
-                    orig++;
-                }
-                if (blocked) continue;
-                for (iTr = 0; iTr < list.size(); iTr++) if (Score > cand[list[iTr]].t.maxScore || (Score == cand[list[iTr]].t.maxScore && c.t.gLength < cand[list[iTr]].t.gLength)) break;
-                if (iTr >= Nmax) { nClass[R_BEHIND_FULL]++; continue; }
-                const u32 need = sizes[k];
-                if (top + need > g.arenaBytes) {
-                    u32 live = 0; for (u32 id : list) live += sizes[id];
-                    const bool freed = live < top; top = live;
-                    if (top + need > g.arenaBytes) { ovf = true; if (run < 2) nClass[R_OVF_CLAUSE1]++; break; }
-                    if (top * 4u > g.arenaBytes * 3u) { ovf = true; if (run < 2) nClass[R_OVF_CLAUSE2]++; break; }
-                    if (freed) nClass[R_COMPACT_FREES]++;
-                }
-                top += need;
-                if (iTr == 0 && list.size() > 64) nClass[R_RANK0_OVER64]++;
-                if (list.size() == Nmax) nClass[R_INSERT_FULL]++;
-                list.insert(list.begin() + iTr, k); if (list.size() > Nmax) list.pop_back();
-            }
+            // stitchWindowAligns.cpp:232-303 one candidate after the other, and the arena's book-keeping (cand_log_ref.h candLogSequential)
+            CandLogStats st; const CandLogResult res = candLogSequential(cand, Nmax, range, chim != 0, minIn, g.arenaBytes, &st);
+            const std::vector<u32> &list = res.list; const bool ovf = res.ovf;
+            nClass[R_LIST_64] += st.list64; if (!g.big) nClass[R_LDS_LIST_64] += st.list64; nClass[R_LIST_128] += st.list128; nClass[R_TAIL] += st.tail; nClass[R_REMOVE_TRIP2] += st.removeTrip2;
+            nClass[R_BEHIND_FULL] += st.behindFull; if (run < 2) { nClass[R_OVF_CLAUSE1] += st.ovfClause1; nClass[R_OVF_CLAUSE2] += st.ovfClause2; } nClass[R_COMPACT_FREES] += st.compactFrees;
+            nClass[R_RANK0_OVER64] += st.rank0Over64; nClass[R_INSERT_FULL] += st.insertFull;
             g.expOverflow = ovf; g.expN = ovf ? 0 : (u32)list.size(); g.expBest = list.empty() ? 0 : cand[list[0]].t.maxScore; g.expOff = S.logExp.size();
             if (!ovf) S.logExp.insert(S.logExp.end(), list.begin(), list.end());
             if (run == 2 && !ovf) nClass[R_BIG_NO_OVF]++;

@@ -2,6 +2,8 @@
 // (No counterpart in the reference: there the per-thread ReadAlign object owns trAll[][] directly.)
 // Output order is deterministic -- reads in batch order, windows in window order, transcripts best-first --
 // so result buffers can be compared byte for byte between runs and against the oracle.
+// Checked kernel by kernel and behind k_stitch_verify / _replay / _finish on batches made by hand (oracle/tail_routines_check.cpp; tests/test_tail_routines.py, gfx950 leg
+// tests/test_gpu_tail_routines.py): both scans against loops, the arrays against Oracle::emitRead byte for byte, the capacity rule with arrays one record short.
 #include "dev.h"
 
 // exclusive scan of (nTr, nEx) over reads, two levels: (1) every block of 256 reads scans itself (coalesced over the batch) and

@@ -1263,6 +1263,7 @@ extern "C" __global__ void __launch_bounds__(256) k_stitch_replay(const DevIndex
 }
 
 // ---- per read: true incoming maxScoreMate of every window; queue the windows whose pass-0 result may differ ----
+// (held to its rule on DWinOut records made by hand, as k_stitch_replay is to the sequential list of its logs: oracle/tail_routines_check.cpp)
 extern "C" __global__ void __launch_bounds__(256) k_stitch_verify(const DevIndex *__restrict__ Xp, DevBatch B) {
     if (B.cursors[CUR_FLAGS] != 0) return;          // a pool overflowed in an earlier kernel: the host grows it and re-runs the batch
     u32 ir = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1328,6 +1329,7 @@ __device__ static ChimSel chimSelectPartner(const staramd_params &P, const DevBa
 // ---- per read: totals, trBest, maxScoreMate (ReadAlign_stitchPieces.cpp:288-348) ----
 // alignTranscriptsPerReadNmax (:290-294) stops the reference's walk before window k when the transcripts recorded so
 // far reach the limit; windows < k do not depend on windows >= k, so the exact result is the prefix.
+// Checked on window lists made by hand against the oracle's rules restated, Oracle::emitRead and the host's partnerOverWindows (oracle/tail_routines_check.cpp).
 extern "C" __global__ void __launch_bounds__(256) k_stitch_finish(const DevIndex *__restrict__ Xp, DevBatch B) {
     if (B.cursors[CUR_FLAGS] != 0) return;          // a pool overflowed in an earlier kernel: the host grows it and re-runs the batch
     const staramd_params &P = Xp->P;
