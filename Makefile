@@ -62,7 +62,7 @@ oracle/_build/liboracle.so: oracle/star_oracle.cpp include/star_amd.h
 	$(CXX) $(CXXFLAGS) -shared oracle/star_oracle.cpp -o $@
 
 # test infrastructure: the index-building algorithm (star_amd/csrc/index/index_core.h) on a plain-loop backend, to check its logic without a GPU
-oracle/_build/libindex_emul.so: oracle/index_emul.cpp $(wildcard star_amd/csrc/index/*.h)
+oracle/_build/libindex_emul.so: oracle/index_emul.cpp oracle/loop_backend.h $(wildcard star_amd/csrc/index/*.h)
 	@mkdir -p oracle/_build
 	$(CXX) $(CXXFLAGS) -fopenmp -shared oracle/index_emul.cpp -o $@
 

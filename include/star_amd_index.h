@@ -54,6 +54,8 @@ typedef struct staramd_sjdb_args {
     const uint8_t *Gsj; uint32_t sjdbN, sjdbLength;
     const uint8_t *isOld; const uint32_t *oldSJind; uint32_t oldSjdbN; uint32_t reserved; uint64_t sjNew;
     uint8_t *SAout; uint64_t saOutCapacity; uint8_t *SAiOut; uint64_t saiOutCapacity;
+    const uint8_t *SAiOld;                                   /* old packed SAindex (its N marks are carried over, sjdbBuildIndex.cpp:251); not read by
+                                                              * staramd_insert_junctions, which has the resident one */
 } staramd_sjdb_args;
 typedef struct staramd_sjdb_result { uint64_t nInd, nSAnew, nSAbyteNew, nSAibyte; float msTotal; uint32_t reserved; } staramd_sjdb_result;
 int staramd_sjdb_insert(int device, const staramd_sjdb_args *a, staramd_sjdb_result *res);

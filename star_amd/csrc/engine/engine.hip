@@ -553,7 +553,7 @@ extern "C" int staramd_insert_junctions(staramd_ctx *c, const staramd_sjdb_args 
     SjdbParams P; P.nGenomeOld = X.nGenome; P.nGenomeReal = a->nGenomeReal; P.nSAold = X.nSA; P.GstrandBit = X.strandBit;
     P.sjdbN = a->sjdbN; P.sjdbLength = a->sjdbLength; P.oldSjdbN = a->oldSjdbN; P.sjNew = a->sjNew; P.saIndexNbases = X.saiNbases;
     SjdbDeviceResult R; memset(&R, 0, sizeof(R));
-    sjdbInsertDevice(be, P, X.G, X.SA, a->Gsj, a->isOld, a->oldSJind, X.saiStart, R, (u64)GPAD);
+    sjdbInsertDevice(be, P, X.G, X.SA, X.SAi, a->Gsj, a->isOld, a->oldSJind, X.saiStart, R, (u64)GPAD);
     memset(res, 0, sizeof(*res));
     res->nInd = R.nInd; res->nSAnew = R.nSAnew;
     res->nSAbyteNew = packedBytes(R.nSAnew, X.saBits); res->nSAibyte = packedBytes(X.saiStart[X.saiNbases], X.saiBits);

@@ -338,6 +338,7 @@ static std::string sjdbPrepareAndBuild(const RunParams &P, GenomeIndex &gi, cons
         a.Gsj = Gsj.data(); a.sjdbN = (uint32_t)sjdbN; a.sjdbLength = (uint32_t)sjdbLength;
         a.isOld = isOld.data(); a.oldSJind = oldSJind.data(); a.oldSjdbN = (uint32_t)oldSjdbN; a.sjNew = sjNew;
         a.SAout = hostArrays ? SA2v.data() : nullptr; a.saOutCapacity = SA2v.size(); a.SAiOut = hostArrays ? SAiNew.data() : nullptr; a.saiOutCapacity = SAiNew.size();
+        a.SAiOld = gi.SAi.data();
         staramd_sjdb_result r;
         int rc = resident ? g_sjdbResidentFn(g_sjdbResidentUser, &a, &r) : g_sjdbDeviceFn(g_sjdbDevice, &a, &r);
         if (rc) return "EXITING because of FATAL ERROR: junction insertion on the MI355X failed (code " + std::to_string(rc) + ")";

@@ -81,7 +81,7 @@ IDX_HD u32 saiClassFast(const u8 *T, u64 pos, u32 L, int &iL4) {
     u32 ind = 0; iL4 = -1;
     for (u32 ii = 0; ii < L; ii++) {
         const u32 g = (u32)((ii < 8 ? w0 >> (8 * ii) : w1 >> (8 * (ii - 8))) & 0xFFu);
-        if (g > 3) { iL4 = (int)ii; ind <<= 2 * (L - ii); return ind; }
+        if (g > 3) { iL4 = (int)ii; if (ii) ind <<= 2 * (L - ii); return ind; }       // (ii == 0: ind is 0, and 2 * L may be the full 32 bits)
         ind = (ind << 2) + g;
     }
     return ind;
@@ -260,9 +260,12 @@ template <class BE> u64 suffixSort(BE &be, const u8 *T, u64 N, u64 *dSA, u64 *dI
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 3. packing: text positions -> the reference's SA values, (GstrandBit+1) bits each, PackedArray layout.
-//    One work item per 64 entries = exactly `bits` 64-bit words.  dOut needs ceil(n/64)*bits words.
+//    One work item per 64 entries = exactly `bits` 64-bit words.  dOut needs packedWords(n, bits) = ceil(n/64)*bits + 2 words: the two behind
+//    the groups are zeroed, because the last of the (n-1)*bits/8 + 8 bytes of the reference's array lie in them when n is a multiple of 64
+//    (PackedArray::allocateArray zeroes its last 8 bytes)
 template <class BE, class V> void packArray(BE &be, u64 n, u32 bits, u64 *dOut, V valueOf) {
     u64 nGroups = (n + 63) / 64;
+    be.forEach(2, [=] IDX_L (u64 k) { dOut[nGroups * bits + k] = 0; });
     be.forEach(nGroups, [=] IDX_L (u64 g) {
         u64 *w = dOut + g * bits;
         u64 acc = 0; u32 fill = 0; u32 wi = 0;
@@ -292,7 +295,15 @@ IDX_HD u64 saValueOfPos(u64 pos, u64 N, u32 GstrandBit) { return pos < N ? pos :
 //      N mark           a run whose first non-ACGT code is at offset <= iL marks the entry of the latest present prefix
 //                       of every length iL1 >= that offset                                   :161-166
 //    Returns 0, or 1 if the first suffix has a non-ACGT code inside the index prefix (the reference runs off its tables then).
-template <class BE> int buildSAindex(BE &be, const u8 *T, const u64 *dSApos, u64 nSA, u32 L, u32 GstrandBit, const u64 *saiStart, u64 *dSAiU) {
+//
+//    After a junction insertion the reference does not walk again: it patches the old table (sjdbBuildIndex.cpp:209-284).  Values and absent flags
+//    come out as the walk over the merged array gives them; the N marks do not.  A present entry of the old table KEEPS its mark (:251), and only the
+//    NEW suffixes mark the latest present prefix of the new table (:262-284) -- an old suffix with N whose latest present prefix is now one that an
+//    inserted junction brought in still marks the old one.  buildSAindexMarked states that: isNew(text position) tells the suffixes that mark, and
+//    dOldPacked is the old packed table whose marks on present entries are carried over.  Generation is the case "every suffix marks, no old table".
+struct SaiEverySuffixMarks { IDX_HD bool operator()(u64) const { return true; } };
+template <class BE, class IsNew> int buildSAindexMarked(BE &be, const u8 *T, const u64 *dSApos, u64 nSA, u32 L, u32 GstrandBit, const u64 *saiStart, u64 *dSAiU,
+                                                        IsNew isNew, const u64 *dOldPacked) {
     const u64 absentBit = 1ull << (GstrandBit + 2), nBit = 1ull << (GstrandBit + 1);
     // ---- run list.  The head flags are computed once, one thread per suffix (two classes = four 8-byte gathers each), and kept as bytes: the two
     // passes of the compaction then stream over them instead of classifying every suffix again, byte by byte, inside a serial loop per chunk
@@ -301,12 +312,14 @@ template <class BE> int buildSAindex(BE &be, const u8 *T, const u64 *dSApos, u64
     be.forEach(nSA, [=] IDX_L (u64 i) {
         if (i == 0) { head[i] = 1; return; }
         int a4, b4; u32 a = saiClassFast(T, dSApos[i], L, a4), b = saiClassFast(T, dSApos[i - 1], L, b4);
-        head[i] = (a != b || a4 != b4) ? 1 : 0;
+        head[i] = (a != b || a4 != b4 || (a4 >= 0 && isNew(dSApos[i]) != isNew(dSApos[i - 1]))) ? 1 : 0;      // a run that marks is all new or all old
     });
     auto isHead = [=] IDX_L (u64 i) { return head[i] != 0; };
     u64 R = compactIf(be, nSA, isHead, [=] IDX_L (u64, u64) {});
-    u64 *runIsa = be.template alloc<u64>(R); u32 *runInd = be.template alloc<u32>(R); int8_t *runL4 = be.template alloc<int8_t>(R);
-    compactIf(be, nSA, isHead, [=] IDX_L (u64 i, u64 o) { int l4; u32 c = saiClassFast(T, dSApos[i], L, l4); runIsa[o] = i; runInd[o] = c; runL4[o] = (int8_t)l4; });
+    u64 *runIsa = be.template alloc<u64>(R); u32 *runInd = be.template alloc<u32>(R); int8_t *runL4 = be.template alloc<int8_t>(R); u8 *runMarks = be.template alloc<u8>(R);
+    compactIf(be, nSA, isHead, [=] IDX_L (u64 i, u64 o) {
+        int l4; u32 c = saiClassFast(T, dSApos[i], L, l4); runIsa[o] = i; runInd[o] = c; runL4[o] = (int8_t)l4; runMarks[o] = (l4 >= 0 && isNew(dSApos[i])) ? 1 : 0;
+    });
     be.free(head);
     int bad = 0;
     { int8_t first; be.copyToHost(&first, runL4, 1); if (first != -1) bad = 1; }
@@ -336,14 +349,21 @@ template <class BE> int buildSAindex(BE &be, const u8 *T, const u64 *dSApos, u64
         // N marks (after all values of this level are in place)
         be.forEach(R, [=] IDX_L (u64 j) {
             int l4 = runL4[j];
-            if (l4 < 0 || (u32)l4 > iL) return;
+            if (l4 < 0 || (u32)l4 > iL || !runMarks[j]) return;
             u64 m = M[j];
             if (m == 0) return;
             be_atomicOr(dSAiU + base + (m - 1), nBit);
         });
     }
-    be.free(M); be.free(runIsa); be.free(runInd); be.free(runL4);
+    be.free(M); be.free(runIsa); be.free(runInd); be.free(runL4); be.free(runMarks);
+    if (dOldPacked && !bad) {
+        const u32 saiBits = GstrandBit + 3;
+        be.forEach(saiStart[L], [=] IDX_L (u64 e) { const u64 o = packedGetW(dOldPacked, e, saiBits); if ((o & nBit) && !(o & absentBit)) dSAiU[e] |= nBit; });
+    }
     return bad;
+}
+template <class BE> int buildSAindex(BE &be, const u8 *T, const u64 *dSApos, u64 nSA, u32 L, u32 GstrandBit, const u64 *saiStart, u64 *dSAiU) {
+    return buildSAindexMarked(be, T, dSApos, nSA, L, GstrandBit, saiStart, dSAiU, SaiEverySuffixMarks(), (const u64 *)nullptr);
 }
 
 } // namespace staridx

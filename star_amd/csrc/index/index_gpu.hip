@@ -51,7 +51,7 @@ extern "C" int staramd_index_build(int device, const uint8_t *G, const staramd_i
 }
 
 extern "C" int staramd_sjdb_insert(int device, const staramd_sjdb_args *a, staramd_sjdb_result *res) {
-    if (!a || !res || !a->G || !a->SA || !a->Gsj || !a->isOld || !a->SAout || !a->SAiOut || (a->oldSjdbN && !a->oldSJind)) { g_idxErr = "staramd_sjdb_insert: null argument"; return STARAMD_ERR_ARG; }
+    if (!a || !res || !a->G || !a->SA || !a->SAiOld || !a->Gsj || !a->isOld || !a->SAout || !a->SAiOut || (a->oldSjdbN && !a->oldSJind)) { g_idxErr = "staramd_sjdb_insert: null argument"; return STARAMD_ERR_ARG; }
     if (a->sjdbN == 0 || a->sjdbLength < 3 || a->gSAindexNbases < 1 || a->gSAindexNbases > 16 || a->nSAold == 0) { g_idxErr = "staramd_sjdb_insert: bad parameters"; return STARAMD_ERR_ARG; }
     int nDev = 0;
     if (hipGetDeviceCount(&nDev) != hipSuccess || nDev == 0) { g_idxErr = "no HIP device visible: junction insertion runs on the GPU only (no CPU fallback in this library)"; return STARAMD_ERR_DEVICE; }
@@ -61,7 +61,7 @@ extern "C" int staramd_sjdb_insert(int device, const staramd_sjdb_args *a, stara
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, be.s);
     SjdbParams P; P.nGenomeOld = a->nGenomeOld; P.nGenomeReal = a->nGenomeReal; P.nSAold = a->nSAold; P.GstrandBit = a->GstrandBit;
     P.sjdbN = a->sjdbN; P.sjdbLength = a->sjdbLength; P.oldSjdbN = a->oldSjdbN; P.sjNew = a->sjNew; P.saIndexNbases = a->gSAindexNbases;
-    SjdbHostArgs A{a->G, a->SA, a->nSAbyteOld, a->Gsj, a->isOld, a->oldSJind, a->SAout, a->saOutCapacity, a->SAiOut, a->saiOutCapacity};
+    SjdbHostArgs A{a->G, a->SA, a->nSAbyteOld, a->Gsj, a->isOld, a->oldSJind, a->SAout, a->saOutCapacity, a->SAiOut, a->saiOutCapacity, a->SAiOld};
     u64 nInd = 0, nb = 0, nbi = 0;
     int rc = sjdbInsertHost(be, P, A, nInd, nb, nbi);
     (void)hipEventRecord(e1, be.s); (void)hipStreamSynchronize(be.s);

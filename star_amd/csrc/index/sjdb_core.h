@@ -7,8 +7,9 @@
 //   sort     :88-101   new suffixes ordered by (insertion point, suffix text up to its spacer, offset)
 //                      (funCompareUintAndSuffixes, source/funCompareUintAndSuffixes.cpp:6-40)
 //   merge    :141-207  old and new entries interleaved into the new packed array, old entries re-based
-//   SAindex  :209-284  patched by the reference; here REBUILT from the merged array with the generation-time builder
-//                      (index_core.h buildSAindex) -- the result is the same table (tests/test_sjdb_device.py)
+//   SAindex  :209-284  patched by the reference; here REBUILT from the merged array with the generation-time builder, which gives the same values
+//                      and absent flags; the N marks follow the patch: marks of the old table's present entries carried over, new marks from the
+//                      new suffixes alone (index_core.h buildSAindexMarked; tests/test_sjdb_device.py, oracle/index_routines_check.cpp)
 // sjdbPrepare (which junctions, their flanking sequences Gsj, motifs, shifts) stays on the host: it is small.
 //
 // Same backend interface as index_core.h: HipBackend is the product, oracle/index_emul.cpp the plain-loop twin for CPU tests.
@@ -75,9 +76,10 @@ struct SjdbDeviceResult {
 };
 
 // dGold: old genome text, base 0 at dGold (SJ_GPAD bytes of 5 readable either side).  dSAold: packed old suffix array (u64 words).
+// dSAiOld: packed old SAindex (whole u64 words readable).
 // hGsj: junction sequences of the NEW table, forward half only: sjdbN blocks of sjdbLength codes, the last code of a block = spacer.
 // hIsOld[sjdbN]: 1 = the junction is already in the old index (no new suffixes).  hOldSJind[oldSjdbN]: new number of every old junction.
-template <class BE> int sjdbInsertDevice(BE &be, const SjdbParams &P, const u8 *dGold, const u64 *dSAold, const u8 *hGsj, const u8 *hIsOld,
+template <class BE> int sjdbInsertDevice(BE &be, const SjdbParams &P, const u8 *dGold, const u64 *dSAold, const u64 *dSAiOld, const u8 *hGsj, const u8 *hIsOld,
                                          const u32 *hOldSJind, const u64 *saiStart, SjdbDeviceResult &R, u64 padOut = SJ_GPAD) {
     const u64 nGsj = (u64)P.sjdbN * P.sjdbLength, nQ = 2 * nGsj + 1;
     const u32 Lsj = P.sjdbLength, GstrandBit = P.GstrandBit, saBits = P.GstrandBit + 1;
@@ -197,7 +199,7 @@ template <class BE> int sjdbInsertDevice(BE &be, const SjdbParams &P, const u8 *
         be.forEach(packedWords(nSAnew + 1, saBits) - nWords, [=] IDX_L (u64 k) { out[nWords + k] = 0; });
         be.free(jnG);
     }
-    be.free(pos); be.free(off); be.free(dOldSJind); be.free(dIsOld);
+    be.free(pos); be.free(off); be.free(dOldSJind);
     be.stage("sjdb: merge");
     // ---- new genome text: chromosomes + forward junction block, spacers either side
     R.dGnew = be.template alloc<u8>(R.nGenomeNew + 2 * padOut);
@@ -224,11 +226,14 @@ template <class BE> int sjdbInsertDevice(BE &be, const SjdbParams &P, const u8 *
         const u64 nSAi = saiStart[P.saIndexNbases];
         u64 *dSAiU = be.template alloc<u64>(nSAi);
         be.stage("sjdb: SAindex text + unpack");
-        R.badFirstSuffix = buildSAindex(be, T, dSApos, nSAnew, P.saIndexNbases, GstrandBit, saiStart, dSAiU);
+        // a suffix is new when it starts inside a junction block that the old index did not have (either strand of the 2N text)
+        auto isNewSuffix = [=] IDX_L (u64 p) { const u64 g = p < N ? p : 2 * N - 1 - p; return g >= nGenomeReal && !dIsOld[(g - nGenomeReal) / Lsj]; };
+        R.badFirstSuffix = buildSAindexMarked(be, T, dSApos, nSAnew, P.saIndexNbases, GstrandBit, saiStart, dSAiU, isNewSuffix, dSAiOld);
         const u64 *su = dSAiU;
         packArray(be, nSAi, GstrandBit + 3, R.dSAiPacked, [=] IDX_L (u64 i) { return su[i]; });
         be.free(dSAiU); be.free(dSApos); be.free(dTraw);
     }
+    be.free(dIsOld);
     be.stage("sjdb: SAindex build + pack");
     return 0;
 }
@@ -237,6 +242,7 @@ template <class BE> int sjdbInsertDevice(BE &be, const SjdbParams &P, const u8 *
 struct SjdbHostArgs {
     const u8 *G; const u8 *SA; u64 nSAbyteOld; const u8 *Gsj; const u8 *isOld; const u32 *oldSJind;
     u8 *SAout; u64 saCap; u8 *SAiOut; u64 saiCap;
+    const u8 *SAiOld;       // the old packed SAindex, packedBytes(saiStart[L], GstrandBit + 3) bytes
 };
 template <class BE> int sjdbInsertHost(BE &be, const SjdbParams &P, const SjdbHostArgs &A, u64 &nInd, u64 &nSAbyteNew, u64 &nSAibyte) {
     u64 saiStart[17]; saiStart[0] = 0;
@@ -248,9 +254,13 @@ template <class BE> int sjdbInsertHost(BE &be, const SjdbParams &P, const SjdbHo
     u64 *dSAold = be.template alloc<u64>(wOld);
     { u64 *w = dSAold; be.forEach(3, [=] IDX_L (u64 i) { w[wOld - 1 - i] = 0; }); }
     be.copyToDevice((u8 *)dSAold, A.SA, A.nSAbyteOld);
+    const u64 saiBytesOld = packedBytes(saiStart[P.saIndexNbases], P.GstrandBit + 3), wiOld = (saiBytesOld + 7) / 8 + 2;
+    u64 *dSAiOld = be.template alloc<u64>(wiOld);
+    { u64 *w = dSAiOld; be.forEach(3, [=] IDX_L (u64 i) { w[wiOld - 1 - i] = 0; }); }
+    be.copyToDevice((u8 *)dSAiOld, A.SAiOld, saiBytesOld);
     SjdbDeviceResult R;
-    sjdbInsertDevice(be, P, dGraw + SJ_GPAD, dSAold, A.Gsj, A.isOld, A.oldSJind, saiStart, R);
-    be.free(dSAold); be.free(dGraw);
+    sjdbInsertDevice(be, P, dGraw + SJ_GPAD, dSAold, dSAiOld, A.Gsj, A.isOld, A.oldSJind, saiStart, R);
+    be.free(dSAold); be.free(dGraw); be.free(dSAiOld);
     nInd = R.nInd;
     nSAbyteNew = packedBytes(R.nSAnew, P.GstrandBit + 1); nSAibyte = packedBytes(saiStart[P.saIndexNbases], P.GstrandBit + 3);
     int rc = R.badFirstSuffix ? -3 : 0;
