@@ -25,18 +25,18 @@ endef
 HOST_SRC := $(wildcard star_amd/csrc/host/*.cpp)
 HOST_LIB_SRC := $(filter-out star_amd/csrc/host/main.cpp star_amd/csrc/host/cli_run.cpp,$(HOST_SRC))
 CLI_SRC := star_amd/csrc/host/main.cpp star_amd/csrc/host/cli_run.cpp
-CLI_HDR := include/star_amd_host.h include/star_amd_index.h include/star_amd_cli.h include/star_amd.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_bgzf.h
+CLI_HDR := include/star_amd_host.h include/star_amd_index.h include/star_amd_cli.h include/star_amd.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_dedup.h include/star_amd_bgzf.h
 HIP_SRC  := $(wildcard star_amd/csrc/engine/*.hip) $(wildcard star_amd/csrc/index/*.hip)
-HIP_HDR  := $(wildcard star_amd/csrc/engine/*.h) $(wildcard star_amd/csrc/index/*.h) star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_index.h include/star_amd_bamsort.h include/star_amd_signal.h
+HIP_HDR  := $(wildcard star_amd/csrc/engine/*.h) $(wildcard star_amd/csrc/index/*.h) star_amd/csrc/chim_pair.h star_amd/csrc/bam_aux.h star_amd/csrc/dedup_rule.h include/star_amd.h include/star_amd_index.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_dedup.h
 
 all: host engine shadow cli oracle
 
 host: star_amd/lib/libstaramd_host.so
 engine: star_amd/lib/libstaramd.so
 cli: star_amd/bin/star_amd star_amd/lib/libstaramd_cli.so
-oracle: oracle/_build/liboracle.so oracle/_build/libindex_emul.so oracle/_build/star_amd_oracle_cli oracle/_build/libstaramd_cli_oracle.so oracle/_build/libstaramd_cli_replay.so oracle/_build/libstaramd_emul.so oracle/_build/star_amd_emul_cli
+oracle: oracle/_build/liboracle.so oracle/_build/libindex_emul.so oracle/_build/star_amd_oracle_cli oracle/_build/libstaramd_cli_oracle.so oracle/_build/libstaramd_cli_replay.so oracle/_build/libstaramd_emul.so oracle/_build/star_amd_emul_cli oracle/_build/libstaramd_units_emul.so
 
-star_amd/lib/libstaramd_host.so: $(HOST_LIB_SRC) star_amd/csrc/host/host.h star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_index.h include/star_amd_host.h include/star_amd_bgzf.h include/star_amd_bamsort.h include/star_amd_signal.h
+star_amd/lib/libstaramd_host.so: $(HOST_LIB_SRC) star_amd/csrc/host/host.h star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_index.h include/star_amd_host.h include/star_amd_bgzf.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_dedup.h star_amd/csrc/bam_aux.h star_amd/csrc/dedup_rule.h
 	@mkdir -p star_amd/lib
 	$(CXX) $(CXXFLAGS) -shared $(HOST_LIB_SRC) -o $@ -lz
 
@@ -99,5 +99,18 @@ oracle/_build/libstaramd_emul.so: $(HIP_SRC) $(HIP_HDR) $(wildcard oracle/wave_e
 # binary, device index build and device junction insertion included (tests/test_wave_emul.py)
 oracle/_build/star_amd_emul_cli: $(CLI_SRC) oracle/_build/libstaramd_emul.so star_amd/lib/libstaramd_host.so $(CLI_HDR)
 	$(CXX) $(CXXFLAGS) -fPIE $(CLI_SRC) -o $@ -Lstar_amd/lib -lstaramd_host -Loracle/_build -lstaramd_emul -Wl,-rpath,'$$ORIGIN/../../star_amd/lib' -Wl,-rpath,'$$ORIGIN'
+
+# the four stand-alone device units (k_bgzf, k_bamsort, k_signal, k_dedup) compiled for the host by the wavefront emulator, with its runtime: what the CPU
+# tests of these units build for themselves in a temporary folder (tests/util.py, tests/test_dedup_emul.py); here so that `make` says when a unit stops compiling
+UNITS_EMUL := k_bgzf k_bamsort k_signal k_dedup
+EMUL_CXX ?= /opt/rocm/lib/llvm/bin/clang++
+oracle/_build/libstaramd_units_emul.so: $(foreach u,$(UNITS_EMUL),star_amd/csrc/engine/$(u).hip) $(HIP_HDR) $(wildcard oracle/wave_emul/*.cpp oracle/wave_emul/*.h oracle/wave_emul/hip/*.h oracle/wave_emul/rocprim/*.hpp)
+	@mkdir -p oracle/_build/units_emul
+	@rm -f oracle/_build/units_emul/*.o
+	@set -e; for u in $(UNITS_EMUL); do $(EMUL_CXX) -x c++ -std=c++17 -O1 -fPIC -Wno-unknown-attributes -I oracle/wave_emul -c star_amd/csrc/engine/$$u.hip -o oracle/_build/units_emul/$$u.o & done; \
+	  $(EMUL_CXX) -std=c++17 -O1 -fPIC -D_GNU_SOURCE -c oracle/wave_emul/emu.cpp -o oracle/_build/units_emul/emu.o & \
+	  $(EMUL_CXX) -std=c++17 -O1 -fPIC -c oracle/wave_emul/emu_lds.cpp -o oracle/_build/units_emul/emu_lds.o & wait; \
+	  for u in $(UNITS_EMUL) emu emu_lds; do test -s oracle/_build/units_emul/$$u.o; done
+	$(EMUL_CXX) -shared -fPIC $(foreach u,$(UNITS_EMUL) emu emu_lds,oracle/_build/units_emul/$(u).o) -o $@ -ldl
 
 .PHONY: all host engine shadow cli oracle ref clean

@@ -22,6 +22,7 @@
 #include "star_amd_index.h"
 #include "star_amd_bamsort.h"
 #include "star_amd_signal.h"
+#include "star_amd_dedup.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -77,6 +78,23 @@ void  sah_signal_counts(void *h, uint64_t out[8]);
 /* the host's half of --gpuSignal Device alone (tests): the Signal.* files of the --outWig* flags and --outFileNamePrefix in argv (a command line that
  * sah_create accepts, e.g. the tool mode's) from a staramd_signal_result.  0, or -1 with the text in errbuf */
 int   sah_signal_files_from_runs(int argc, char **argv, int nChr, const char *const *chrName, const uint64_t *chrLength, const void *result, char *errbuf, int errlen);
+/* --gpuBAMdedup Device: the duplicate pairs of --bamRemoveDuplicatesType (the other job of --runMode inputAlignmentsFromBAM) are found by the functions of
+ * include/star_amd_dedup.h; the host applies the bytes that come back to the flag words and writes Processed.out.bam.  The tool mode runs inside
+ * sah_create: install before it.  Process-wide, NULL uninstalls.  A run with Device and nothing installed fails with a text that says so. */
+typedef struct sah_dedup_fns {
+    int (*host_records)(int device, const staramd_dedup_params *params, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, staramd_dedup_result *result);
+    void (*free_result)(staramd_dedup_result *result);
+    const char *(*last_error)(void);
+} sah_dedup_fns;
+void  sah_set_dedup_device(const sah_dedup_fns *fns);
+int   sah_dedup_on_device(void *h);                                     /* 1: --gpuBAMdedup Device */
+/* the duplicate marking of this run: staramd_dedup_result::stats -- [0] records, [1] unique records, [2] pairs, [3] classes, [4] records that end with
+ * 0x400 set, [5] unpaired unique records, [6] nanoseconds of the device's kernels, [7] of its copies (both 0 on the Host path) */
+void  sah_dedup_counts(void *h, uint64_t out[8]);
+/* the Host path's rule alone (tests): staramd_dedup_host_records without a device -- same record convention, same result (stats[6..7] are 0); the result is
+ * released with sah_dedup_host_free.  0, or -1 when a record lies outside the bytes or the result cannot be allocated */
+int   sah_dedup_host_records(const staramd_dedup_params *params, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, staramd_dedup_result *result);
+void  sah_dedup_host_free(staramd_dedup_result *result);
 /* chimeric detection (--chimSegmentMin > 0, --chimMultimapNmax 0, no merging of overlapping mates): the engine runs the partner loop (staramd_params::resultSelect 2)
  * instead of returning every transcript of every window.  Call before the engine contexts are created, when staramd_capabilities() has STARAMD_CAP_CHIM_SELECT;
  * returns 1 when the run's parameters now say so, 0 when they do not qualify. */

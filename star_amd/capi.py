@@ -287,6 +287,18 @@ class HostRun:
         self.L.sah_signal_counts(self.h, out)
         return list(out)
 
+    def dedup_on_device(self):
+        """True: --gpuBAMdedup Device"""
+        self.L.sah_dedup_on_device.restype = C.c_int; self.L.sah_dedup_on_device.argtypes = [C.c_void_p]
+        return bool(self.L.sah_dedup_on_device(self.h))
+
+    def dedup_counts(self):
+        """sah_dedup_counts: [records, unique records, pairs, classes, records marked, unpaired unique records, ns of the device's kernels, ns of its copies]"""
+        self.L.sah_dedup_counts.restype = None; self.L.sah_dedup_counts.argtypes = [C.c_void_p, u64p]
+        out = (C.c_uint64 * 8)()
+        self.L.sah_dedup_counts(self.h, out)
+        return list(out)
+
     def bamsort_budget(self):
         """--gpuBAMsortHBM: what the run's BamSortDevice is to be created with"""
         self.L.sah_bamsort_budget.restype = C.c_uint64; self.L.sah_bamsort_budget.argtypes = [C.c_void_p]
@@ -684,6 +696,90 @@ def signal_files_from_runs(argv, chr_names, chr_length, runs, norm, chr_has, pas
     err = C.create_string_buffer(4096)
     L.sah_signal_files_from_runs(len(args), (C.c_char_p * len(args))(*args), len(names), (C.c_char_p * max(len(names), 1))(*names), (C.c_uint64 * max(len(names), 1))(*chr_length), C.byref(res), err, 4096)
     return err.value.decode()
+
+
+class DedupParams(C.Structure):
+    """staramd_dedup_params (include/star_amd_dedup.h)"""
+    _fields_ = [("markMulti", C.c_int32), ("mate2basesN", C.c_uint32)]
+
+
+class DedupResult(C.Structure):
+    """staramd_dedup_result"""
+    _fields_ = [("dup", C.POINTER(C.c_uint8)), ("nRecords", C.c_uint64), ("fatal", C.c_int32), ("fatalRecord", C.c_uint64), ("stats", C.c_uint64 * 8)]
+
+
+class DedupFns(C.Structure):
+    """sah_dedup_fns (include/star_amd_host.h)"""
+    _fields_ = [("host_records", C.c_void_p), ("free_result", C.c_void_p), ("last_error", C.c_void_p)]
+
+
+class DedupDevice:
+    """include/star_amd_dedup.h: the duplicate pairs of --bamRemoveDuplicatesType on the MI355X (k_dedup.hip in libstaramd.so); lib_path: another library
+    with that ABI (the wave emulator's build in the CPU tests)."""
+
+    def __init__(self, device=0, lib_path=None):
+        L = C.CDLL(lib_path or _need(ENGINE_PATH))
+        L.staramd_dedup_host_records.restype = C.c_int
+        L.staramd_dedup_host_records.argtypes = [C.c_int, C.POINTER(DedupParams), C.c_void_p, C.c_uint64, u64p, C.c_uint64, C.POINTER(DedupResult)]
+        L.staramd_dedup_free.restype = None; L.staramd_dedup_free.argtypes = [C.POINTER(DedupResult)]
+        L.staramd_dedup_constant.restype = C.c_uint32; L.staramd_dedup_constant.argtypes = [C.c_int]
+        L.staramd_dedup_last_error.restype = C.c_char_p
+        self.L = L
+        self.device = device
+        self.workgroup = L.staramd_dedup_constant(0)
+        self.workgroups_per_cu = L.staramd_dedup_constant(1)
+
+    def max_workgroups(self):
+        """STARAMD_DEDUP_MAX_WORKGROUPS as the next call will read it (0: not set, the default of workgroups_per_cu per CU holds)"""
+        return self.L.staramd_dedup_constant(2)
+
+    def host_records(self, records, mark_multi=True, mate2bases_n=0):
+        """records: list of BAM records (bytes, each with its block_size word) in coordinate order.  Returns (dup bytes or None when fatal, fatal, fatalRecord, stats)"""
+        dev = self.device
+        return _dedup_call(lambda p, buf, n_bytes, offs, n, res: self.L.staramd_dedup_host_records(dev, p, buf, n_bytes, offs, n, res), self.L.staramd_dedup_free,
+                           lambda: "staramd_dedup_host_records failed: %s" % self.L.staramd_dedup_last_error().decode(), records, mark_multi, mate2bases_n)
+
+    def install(self):
+        """sah_set_dedup_device with this library's functions (process-wide).  The tool mode runs inside HostRun(): install before it"""
+        L = host_lib()
+        L.sah_set_dedup_device.restype = None; L.sah_set_dedup_device.argtypes = [C.c_void_p]
+        names = ("staramd_dedup_host_records", "staramd_dedup_free", "staramd_dedup_last_error")
+        self._fns = DedupFns(*[C.cast(getattr(self.L, n), C.c_void_p) for n in names])
+        L.sah_set_dedup_device(C.byref(self._fns))
+
+    @staticmethod
+    def uninstall():
+        L = host_lib()
+        L.sah_set_dedup_device.restype = None; L.sah_set_dedup_device.argtypes = [C.c_void_p]
+        L.sah_set_dedup_device(None)
+
+
+def _dedup_call(call, free, error_text, records, mark_multi, mate2bases_n):
+    """the records laid out as the two entries of the duplicate marking take them (bytes + offsets), one call, the result as Python values and released"""
+    blob = b"".join(records)
+    offs, o = [], 0
+    for r in records:
+        offs.append(o); o += len(r)
+    p = DedupParams(1 if mark_multi else 0, mate2bases_n)
+    res = DedupResult()
+    buf = C.create_string_buffer(blob, max(len(blob), 1))
+    if call(C.byref(p), buf, len(blob), (C.c_uint64 * max(len(offs), 1))(*offs), len(offs), C.byref(res)) != 0:
+        raise RuntimeError(error_text())
+    try:
+        dup = C.string_at(res.dup, res.nRecords) if res.dup and not res.fatal else (b"" if not res.fatal else None)
+        return dup, res.fatal, res.fatalRecord, list(res.stats)
+    finally:
+        free(C.byref(res))
+
+
+def dedup_host(records, mark_multi=True, mate2bases_n=0):
+    """the host path's rule alone (dedupOnHost of host/dedup.cpp) on records in memory: what DedupDevice.host_records returns"""
+    L = host_lib()
+    L.sah_dedup_host_records.restype = C.c_int
+    L.sah_dedup_host_records.argtypes = [C.POINTER(DedupParams), C.c_void_p, C.c_uint64, u64p, C.c_uint64, C.POINTER(DedupResult)]
+    L.sah_dedup_host_free.restype = None; L.sah_dedup_host_free.argtypes = [C.POINTER(DedupResult)]
+    return _dedup_call(L.sah_dedup_host_records, L.sah_dedup_host_free, lambda: "sah_dedup_host_records failed: a record lies outside the bytes, or no memory for the result",
+                       records, mark_multi, mate2bases_n)
 
 
 class device_sjdb_insertion:

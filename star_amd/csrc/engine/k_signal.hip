@@ -25,6 +25,7 @@
 #include <algorithm>
 #include "../../../include/star_amd_signal.h"
 #include "bamsort_resident.h"
+#include "../bam_aux.h"
 
 namespace {
 
@@ -39,36 +40,12 @@ static_assert(P >= 1 && 32 % P == 0 && CHUNK <= NT && WORDS <= NT, "a lane's pos
 __device__ __forceinline__ uint64_t packSpan(uint32_t nh, uint32_t strand, uint32_t first, uint32_t last) { return (uint64_t)nh | (uint64_t)strand << 32 | (uint64_t)first << 33 | (uint64_t)last << 43; }
 
 __device__ __forceinline__ uint32_t ld32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }      // records lie at arbitrary byte addresses
-__device__ __forceinline__ uint32_t ld16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
 
 // the NH attribute of a record of `lim` bytes (auxInt of host/signal.cpp, with every read held inside the record): false = absent
+// (the walk itself is bamAuxInts of bam_aux.h, which k_dedup.hip shares)
 __device__ bool auxNH(const uint8_t *rec, uint64_t lim, uint64_t a, uint32_t &val) {
-#pragma unroll 1
-    while (a + 3 <= lim) {
-        const uint8_t t = rec[a + 2]; const bool hit = rec[a] == 'N' && rec[a + 1] == 'H';
-        a += 3;
-        uint64_t w;
-        switch (t) {
-            case 'A': case 'c': case 'C': w = 1; break;
-            case 's': case 'S': w = 2; break;
-            case 'i': case 'I': case 'f': w = 4; break;
-            case 'Z': case 'H': { uint64_t j = a; while (j < lim && rec[j] != 0) j++; w = j - a + 1; break; }
-            case 'B': { if (a + 5 > lim) return false;
-                        const uint8_t bt = rec[a]; const uint32_t n = ld32(rec + a + 1); w = 5 + (uint64_t)n * (bt == 'c' || bt == 'C' ? 1 : bt == 's' || bt == 'S' ? 2 : 4); break; }
-            default: return false;
-        }
-        if (hit) {
-            val = 0;
-            if (a + w <= lim) {
-                if (t == 'c') val = (uint32_t)(int32_t)(int8_t)rec[a]; else if (t == 'C') val = rec[a];
-                else if (t == 's') val = (uint32_t)(int32_t)(int16_t)ld16(rec + a); else if (t == 'S') val = ld16(rec + a);
-                else if (t == 'i' || t == 'I') val = ld32(rec + a);
-            }
-            return true;
-        }
-        a += w;
-    }
-    return false;
+    uint32_t none = 0;
+    return bamAuxInts(rec, lim, a, 'N', 'H', val, false, 0, 0, none) != 0;
 }
 
 struct SigArgs { int32_t type, strand; uint32_t nChr, tileBits; const uint32_t *chrLength, *wanted; };

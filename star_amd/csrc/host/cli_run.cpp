@@ -59,6 +59,10 @@
 #pragma weak staramd_bamsort_finish_signal
 #pragma weak staramd_signal_free
 #pragma weak staramd_signal_last_error
+// and the duplicate marking on the device (k_dedup.hip, sah_set_dedup_device)
+#pragma weak staramd_dedup_host_records
+#pragma weak staramd_dedup_free
+#pragma weak staramd_dedup_last_error
 
 namespace {
 typedef std::chrono::steady_clock Clock;
@@ -517,6 +521,30 @@ struct Pipeline {
         return exitCode;
     }
 };
+
+// --runMode inputAlignmentsFromBAM --bamRemoveDuplicatesType writes Processed.out.bam inside sah_create: with --gpuBAMcompression Device the compressor has to be
+// there before it (a run that maps creates its compressor with its engines, Engines::create; the tool mode's other job, --outWigType, writes no BAM and
+// gets none).  Released when the tool mode is over
+struct ToolBgzf {
+    staramd_bgzf *bgzf = nullptr;
+    // 0, or the exit code of the run
+    int create(const CliFlags &flags) {
+        bool tool = false, dev = false, dedup = false, wig = false;
+        for (size_t i = 0; i + 1 < flags.rest.size(); i++) {
+            const std::string a = flags.rest[i], b = flags.rest[i + 1];
+            if (a == "--runMode" && b == "inputAlignmentsFromBAM") tool = true;
+            if (a == "--gpuBAMcompression" && b == "Device") dev = true;
+            if (a == "--bamRemoveDuplicatesType" && b != "-") dedup = true;
+            if (a == "--outWigType" && b != "None") wig = true;
+        }
+        if (!tool || !dev || !dedup || wig || !(staramd_bgzf_create && staramd_bgzf_compress && staramd_bgzf_destroy && staramd_bgzf_last_error)) return 0;
+        const int device = flags.devices.empty() ? 0 : flags.devices[0];
+        if (staramd_bgzf_create(&bgzf, device, 0)) { bgzf = nullptr; fprintf(stderr, "\nEXITING because of FATAL ERROR: cannot initialise the BGZF compressor on device %d: %s\n", device, staramd_bgzf_last_error()); return 105; }
+        sah_set_bgzf_device_fn(staramd_bgzf_compress, bgzf);
+        return 0;
+    }
+    ~ToolBgzf() { if (bgzf) { sah_set_bgzf_device_fn(nullptr, nullptr); staramd_bgzf_destroy(bgzf); } }
+};
 }
 
 int staramd_cli_main(int argc, char **argv, const staramd_cli_hooks *hooks, staramd_cli_report *report) {
@@ -528,6 +556,12 @@ int staramd_cli_main(int argc, char **argv, const staramd_cli_hooks *hooks, star
         static const sah_signal_fns fns = {staramd_signal_host_records, staramd_bamsort_finish_signal, staramd_signal_free, staramd_signal_last_error};
         sah_set_signal_device(&fns);
     }
+    if (staramd_dedup_host_records && staramd_dedup_free && staramd_dedup_last_error) {      // --gpuBAMdedup Device; likewise before sah_create
+        static const sah_dedup_fns fns = {staramd_dedup_host_records, staramd_dedup_free, staramd_dedup_last_error};
+        sah_set_dedup_device(&fns);
+    }
+    ToolBgzf toolBgzf;
+    if (const int rc = toolBgzf.create(flags)) return rc;
     LoadLock loadLock;
     loadLock.take();
     sah_set_batch_alloc(staramd_pinned_alloc, staramd_pinned_free);      // batch arrays in page-locked memory: the uploads are DMA transfers

@@ -181,6 +181,9 @@ struct RunParams {
     bool runDirPermAll = false, genomeLoadShared = false;
     // --runMode genomeGenerate (genome_generate.cpp): FASTA -> genomeDir, suffix array + SAindex built on the device
     bool runModeGenerate = false; std::vector<std::string> genomeFastaFiles; uint32_t genomeSAindexNbases = 14, genomeChrBinNbits = 18, genomeSAsparseD = 1;
+    std::string bamRemoveDuplicatesType = "-";          // --bamRemoveDuplicatesType - | UniqueIdentical | UniqueIdenticalNotMulti (the tool mode; alignReads ignores it, as the reference does)
+    uint32_t bamRemoveDuplicatesMate2basesN = 0;        // --bamRemoveDuplicatesMate2basesN
+    bool gpuDedupDevice = false;                        // --gpuBAMdedup Device: the duplicate pairs are found on the MI355X (sah_set_dedup_device)
     bool runModeFromBAM = false; std::string inputBAMfile;   // --runMode inputAlignmentsFromBAM --inputBAMfile: signal tracks from an existing BAM, no mapping
     std::string varVCFfile; bool varHeteroOnly = false, wasp = false; const struct Variation *var = nullptr;   // --varVCFfile, --waspOutputMode SAMtag (Parameters.cpp:854-890)
     int readFilesSAMmates = 0;           // --readFilesType SAM SE | PE: 1 | 2 (0 = Fastx)
@@ -469,6 +472,24 @@ struct SignalDeviceParams {
     void set(const RunParams &P, const std::vector<std::string> &chrName, const std::vector<uint64_t> &chrLength);
 };
 std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, const std::string &sigFileName);   // --runMode inputAlignmentsFromBAM
+// a whole BAM file inflated into memory, for the two jobs of --runMode inputAlignmentsFromBAM: d = the BAM byte stream, its first headerEnd bytes the header
+// (magic, text, reference list) as read; recs = every whole record (at its block_size word), in the file's order.  load: error text or ""
+struct BamFileInMemory {
+    std::vector<char> d; size_t headerEnd = 0;
+    std::vector<std::string> chrName; std::vector<uint64_t> chrLength;
+    std::vector<const char *> recs;
+    std::string load(const std::string &bamPath);
+};
+
+// ---- dedup.cpp: --bamRemoveDuplicatesType in the tool mode (source/bamRemoveDuplicates.cpp; the rule: DESIGN.md 7.6, star_amd/csrc/dedup_rule.h)
+// the functions behind --gpuBAMdedup Device (sah_set_dedup_device; nullptr while none is installed)
+void setDedupDeviceFns(const ::sah_dedup_fns *fns);
+const ::sah_dedup_fns *dedupDeviceFns();
+inline constexpr const char *DEDUP_DEVICE_MISSING = "EXITING because of fatal PARAMETERS error: --gpuBAMdedup Device, but no device duplicate-marking functions are installed (sah_set_dedup_device)";
+// the rule on records in memory (record i: recs[i], at its block_size word): what include/star_amd_dedup.h returns, with malloc'ed dup; stats[6..7] stay 0.  false: no memory for the result
+bool dedupOnHost(const std::vector<const char *> &recs, bool markMulti, uint32_t mate2basesN, staramd_dedup_result &out);
+// marks the duplicates of bamPath and writes outPath (Processed.out.bam); counts: sah_dedup_counts.  Error text or ""
+std::string dedupFromBamFile(const RunParams &P, const std::string &bamPath, const std::string &outPath, uint64_t counts[8]);
 
 // ---- bam_sorted.cpp: Aligned.sortedByCoord.out.bam, and what the end of a run shares with it
 // one late line appended to Log.out or Log.progress.out (their start is written by Runner::init; the reference's log is not reproduced)

@@ -284,6 +284,13 @@ std::string RunParams::parse(int argc, char **argv) {
         else if (k == "gpuBAMsort") { const std::string &s = one(k, v); if (s == "Device") gpuBAMsortDevice = true; else if (s == "Host") gpuBAMsortDevice = false; else err = "EXITING: --gpuBAMsort takes Host or Device"; }
         else if (k == "gpuBAMsortHBM") gpuBAMsortHBM = (uint64_t)U(k, v);
         else if (k == "gpuSignal") { const std::string &s = one(k, v); if (s == "Device") gpuSignalDevice = true; else if (s == "Host") gpuSignalDevice = false; else err = "EXITING: --gpuSignal takes Host or Device"; }
+        else if (k == "gpuBAMdedup") { const std::string &s = one(k, v); if (s == "Device") gpuDedupDevice = true; else if (s == "Host") gpuDedupDevice = false; else err = "EXITING: --gpuBAMdedup takes Host or Device"; }
+        else if (k == "bamRemoveDuplicatesType") {      // Parameters.cpp:565-580
+            bamRemoveDuplicatesType = one(k, v);
+            if (bamRemoveDuplicatesType != "-" && bamRemoveDuplicatesType != "UniqueIdentical" && bamRemoveDuplicatesType != "UniqueIdenticalNotMulti")
+                err = "EXITING because of fatal PARAMETERS error: unrecognized option in of --bamRemoveDuplicatesType=" + bamRemoveDuplicatesType + "\nSOLUTION: use allowed option: - or UniqueIdentical or UniqueIdenticalNotMulti";
+        }
+        else if (k == "bamRemoveDuplicatesMate2basesN") bamRemoveDuplicatesMate2basesN = (uint32_t)U(k, v);
         else if (k == "gpuResultSelect") { const std::string &s = one(k, v); if (s == "All") dev.resultSelect = 0; else if (s == "Selected") dev.resultSelect = 1; else err = "EXITING: --gpuResultSelect takes All or Selected"; }
         else if (k == "outFilterIntronMotifs") { const std::string &s = one(k, v); if (s == "None") dev.outFilterIntronMotifs = 0; else if (s == "RemoveNoncanonical") dev.outFilterIntronMotifs = 1; else if (s == "RemoveNoncanonicalUnannotated") dev.outFilterIntronMotifs = 2; else err = "EXITING because of FATAL INPUT error: unrecognized value of --outFilterIntronMotifs=" + s; }
         else if (k == "outFilterIntronStrands") { const std::string &s = one(k, v); if (s == "RemoveInconsistentStrands") dev.outFilterIntronStrandsRemoveInconsistent = 1; else if (s == "None") dev.outFilterIntronStrandsRemoveInconsistent = 0; else err = "EXITING: unsupported --outFilterIntronStrands " + s; }
@@ -366,7 +373,7 @@ std::string RunParams::parse(int argc, char **argv) {
         return "";
     }
     if (runModeFromBAM) {                    // Parameters.cpp:585-605
-        if (!wig.yes) return "EXITING because of fatal INPUT error: at the moment --runMode inputFromBAM only works with --outWigType bedGraph OR --bamRemoveDuplicatesType Identical\nSOLUTION: re-run STAR with --outWigType bedGraph (duplicate removal is not implemented here)\n";
+        if (!wig.yes && bamRemoveDuplicatesType == "-") return "EXITING because of fatal INPUT error: at the moment --runMode inputFromBAM only works with --outWigType bedGraph OR --bamRemoveDuplicatesType Identical\nSOLUTION: re-run STAR with --outWigType bedGraph\n";
         if (inputBAMfile.empty()) return "EXITING because of fatal INPUT error: --runMode inputAlignmentsFromBAM needs --inputBAMfile";
         return "";                                                  // (--gpuSignal Device: wig.yes holds already)
     }

@@ -157,6 +157,7 @@ struct Runner {
     Stats stats;
     FILE *samOut = nullptr;
     bool toolDone = false;                          // --runMode inputAlignmentsFromBAM: everything happened in init()
+    uint64_t dedupCounts[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // sah_dedup_counts
     bool generateMode = false; GenerateJob genJob;  // --runMode genomeGenerate: FASTA scanned in init(), SA / SAindex built by the caller on the device
     FILE *chimOut = nullptr;                        // Chimeric.out.junction
     FILE *chimSamOut = nullptr;                     // Chimeric.out.sam (--chimOutType SeparateSAMold)
@@ -219,7 +220,9 @@ struct Runner {
             return error.empty();
         }
         if (P.runModeFromBAM) {                                     // a tool mode: no index, no reads, no engine
-            error = signalFromBamFile(P, P.inputBAMfile, P.outFileNamePrefix + "Signal");
+            // Parameters.cpp:587-599: the tracks when --outWigType asks for them, else the duplicate marking
+            if (P.wig.yes) error = signalFromBamFile(P, P.inputBAMfile, P.outFileNamePrefix + "Signal");
+            else error = dedupFromBamFile(P, P.inputBAMfile, P.outFileNamePrefix + "Processed.out.bam", dedupCounts);
             toolDone = true;
             return error.empty();
         }
@@ -714,6 +717,21 @@ void sah_set_bamsort_device(const sah_bamsort_fns *fns, staramd_bamsort *sorter)
 void sah_set_signal_device(const sah_signal_fns *fns) { staramd::setSignalDeviceFns(fns); }
 int sah_signal_on_device(void *h) { return ((Runner *)h)->P.gpuSignalDevice ? 1 : 0; }
 void sah_signal_counts(void *h, uint64_t out[8]) { for (int i = 0; i < 8; i++) out[i] = ((Runner *)h)->sorted.signalCounts[i]; }
+void sah_set_dedup_device(const sah_dedup_fns *fns) { staramd::setDedupDeviceFns(fns); }
+int sah_dedup_on_device(void *h) { return ((Runner *)h)->P.gpuDedupDevice ? 1 : 0; }
+void sah_dedup_counts(void *h, uint64_t out[8]) { for (int i = 0; i < 8; i++) out[i] = ((Runner *)h)->dedupCounts[i]; }
+int sah_dedup_host_records(const staramd_dedup_params *params, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, staramd_dedup_result *result) {
+    std::vector<const char *> recs(n);
+    for (uint64_t i = 0; i < n; i++) {
+        uint32_t bs = 0;
+        if (offsets[i] > nBytes || nBytes - offsets[i] < 4) return -1;
+        memcpy(&bs, bytes + offsets[i], 4);
+        if (nBytes - offsets[i] - 4 < bs) return -1;
+        recs[i] = (const char *)bytes + offsets[i];
+    }
+    return staramd::dedupOnHost(recs, params->markMulti != 0, params->mate2basesN, *result) ? 0 : -1;
+}
+void sah_dedup_host_free(staramd_dedup_result *result) { if (result) { free(result->dup); memset(result, 0, sizeof(*result)); } }
 int sah_signal_files_from_runs(int argc, char **argv, int nChr, const char *const *chrName, const uint64_t *chrLength, const void *result, char *errbuf, int errlen) {
     staramd::RunParams P;
     std::string e = P.parse(argc, argv);

@@ -203,12 +203,11 @@ std::string signalFromRuns(const RunParams &P, const std::vector<std::string> &c
     return "";
 }
 
-// --runMode inputAlignmentsFromBAM --inputBAMfile x.bam --outWigType ... (Parameters.cpp:585-592): the same tracks from a coordinate-sorted BAM file.
-// The file is inflated block by block (BGZF = concatenated gzip members) and held in memory; chromosome names and lengths come from its header.
-std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, const std::string &sigFileName) {
+// The input of --runMode inputAlignmentsFromBAM, for both of its jobs (the tracks below, the duplicate marking of dedup.cpp): the file is inflated block by
+// block (BGZF = concatenated gzip members) and held in memory; chromosome names and lengths come from its header.
+std::string BamFileInMemory::load(const std::string &bamPath) {
     gzFile in = gzopen(bamPath.c_str(), "rb");
     if (!in) return "EXITING because of fatal INPUT error: could not open --inputBAMfile " + bamPath;
-    std::vector<char> d;
     for (;;) {
         const size_t old = d.size(), block = 1u << 24;
         d.resize(old + block);
@@ -222,7 +221,6 @@ std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, co
     size_t p = 8 + rd32(d.data() + 4);
     if (p + 4 > d.size()) return "EXITING because of fatal INPUT error: truncated BAM header in " + bamPath;
     const uint32_t nRef = rd32(d.data() + p); p += 4;
-    std::vector<std::string> chrName; std::vector<uint64_t> chrLength;
     for (uint32_t i = 0; i < nRef; i++) {
         if (p + 4 > d.size()) return "EXITING because of fatal INPUT error: truncated BAM header in " + bamPath;
         const uint32_t ln = rd32(d.data() + p); p += 4;
@@ -230,13 +228,24 @@ std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, co
         chrName.emplace_back(d.data() + p, ln ? ln - 1 : 0); p += ln;
         chrLength.push_back(rd32(d.data() + p)); p += 4;
     }
-    std::vector<const char *> recs;
+    headerEnd = p;
     while (p + 4 <= d.size()) {
         const uint32_t bs = rd32(d.data() + p);
         if (p + 4 + bs > d.size()) break;
         recs.push_back(d.data() + p);
         p += 4 + bs;
     }
+    return "";
+}
+
+// --runMode inputAlignmentsFromBAM --inputBAMfile x.bam --outWigType ... (Parameters.cpp:585-592): the same tracks from a coordinate-sorted BAM file.
+std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, const std::string &sigFileName) {
+    BamFileInMemory bam;
+    const std::string loadErr = bam.load(bamPath);
+    if (!loadErr.empty()) return loadErr;
+    const std::vector<char> &d = bam.d;
+    const std::vector<std::string> &chrName = bam.chrName; const std::vector<uint64_t> &chrLength = bam.chrLength;
+    const std::vector<const char *> &recs = bam.recs;
     if (P.gpuSignalDevice) {                                        // --gpuSignal Device: the inflated records go to the device as they are
         const sah_signal_fns *fns = signalDeviceFns();
         if (!fns) return SIGNAL_DEVICE_MISSING;
