@@ -25,9 +25,9 @@ endef
 HOST_SRC := $(wildcard star_amd/csrc/host/*.cpp)
 HOST_LIB_SRC := $(filter-out star_amd/csrc/host/main.cpp star_amd/csrc/host/cli_run.cpp,$(HOST_SRC))
 CLI_SRC := star_amd/csrc/host/main.cpp star_amd/csrc/host/cli_run.cpp
-CLI_HDR := include/star_amd_host.h include/star_amd_index.h include/star_amd_cli.h include/star_amd.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_dedup.h include/star_amd_bgzf.h
+CLI_HDR := include/star_amd_host.h include/star_amd_index.h include/star_amd_cli.h include/star_amd.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_dedup.h include/star_amd_inflate.h include/star_amd_bgzf.h
 HIP_SRC  := $(wildcard star_amd/csrc/engine/*.hip) $(wildcard star_amd/csrc/index/*.hip)
-HIP_HDR  := $(wildcard star_amd/csrc/engine/*.h) $(wildcard star_amd/csrc/index/*.h) star_amd/csrc/chim_pair.h star_amd/csrc/bam_aux.h star_amd/csrc/dedup_rule.h include/star_amd.h include/star_amd_index.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_dedup.h
+HIP_HDR  := $(wildcard star_amd/csrc/engine/*.h) $(wildcard star_amd/csrc/index/*.h) star_amd/csrc/chim_pair.h star_amd/csrc/bam_aux.h star_amd/csrc/dedup_rule.h include/star_amd.h include/star_amd_index.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_dedup.h include/star_amd_inflate.h
 
 all: host engine shadow cli oracle
 
@@ -36,7 +36,7 @@ engine: star_amd/lib/libstaramd.so
 cli: star_amd/bin/star_amd star_amd/lib/libstaramd_cli.so
 oracle: oracle/_build/liboracle.so oracle/_build/libindex_emul.so oracle/_build/star_amd_oracle_cli oracle/_build/libstaramd_cli_oracle.so oracle/_build/libstaramd_cli_replay.so oracle/_build/libstaramd_emul.so oracle/_build/star_amd_emul_cli oracle/_build/libstaramd_units_emul.so
 
-star_amd/lib/libstaramd_host.so: $(HOST_LIB_SRC) star_amd/csrc/host/host.h star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_index.h include/star_amd_host.h include/star_amd_bgzf.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_dedup.h star_amd/csrc/bam_aux.h star_amd/csrc/dedup_rule.h
+star_amd/lib/libstaramd_host.so: $(HOST_LIB_SRC) star_amd/csrc/host/host.h star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_index.h include/star_amd_host.h include/star_amd_bgzf.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_dedup.h include/star_amd_inflate.h star_amd/csrc/bam_aux.h star_amd/csrc/dedup_rule.h
 	@mkdir -p star_amd/lib
 	$(CXX) $(CXXFLAGS) -shared $(HOST_LIB_SRC) -o $@ -lz
 
@@ -100,9 +100,9 @@ oracle/_build/libstaramd_emul.so: $(HIP_SRC) $(HIP_HDR) $(wildcard oracle/wave_e
 oracle/_build/star_amd_emul_cli: $(CLI_SRC) oracle/_build/libstaramd_emul.so star_amd/lib/libstaramd_host.so $(CLI_HDR)
 	$(CXX) $(CXXFLAGS) -fPIE $(CLI_SRC) -o $@ -Lstar_amd/lib -lstaramd_host -Loracle/_build -lstaramd_emul -Wl,-rpath,'$$ORIGIN/../../star_amd/lib' -Wl,-rpath,'$$ORIGIN'
 
-# the four stand-alone device units (k_bgzf, k_bamsort, k_signal, k_dedup) compiled for the host by the wavefront emulator, with its runtime: what the CPU
+# the five stand-alone device units (k_bgzf, k_bamsort, k_signal, k_dedup, k_inflate) compiled for the host by the wavefront emulator, with its runtime: what the CPU
 # tests of these units build for themselves in a temporary folder (tests/util.py, tests/test_dedup_emul.py); here so that `make` says when a unit stops compiling
-UNITS_EMUL := k_bgzf k_bamsort k_signal k_dedup
+UNITS_EMUL := k_bgzf k_bamsort k_signal k_dedup k_inflate
 EMUL_CXX ?= /opt/rocm/lib/llvm/bin/clang++
 oracle/_build/libstaramd_units_emul.so: $(foreach u,$(UNITS_EMUL),star_amd/csrc/engine/$(u).hip) $(HIP_HDR) $(wildcard oracle/wave_emul/*.cpp oracle/wave_emul/*.h oracle/wave_emul/hip/*.h oracle/wave_emul/rocprim/*.hpp)
 	@mkdir -p oracle/_build/units_emul

@@ -23,6 +23,7 @@
 #include "star_amd_bamsort.h"
 #include "star_amd_signal.h"
 #include "star_amd_dedup.h"
+#include "star_amd_inflate.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -95,6 +96,16 @@ void  sah_dedup_counts(void *h, uint64_t out[8]);
  * released with sah_dedup_host_free.  0, or -1 when a record lies outside the bytes or the result cannot be allocated */
 int   sah_dedup_host_records(const staramd_dedup_params *params, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, staramd_dedup_result *result);
 void  sah_dedup_host_free(staramd_dedup_result *result);
+/* --gpuBAMinflate Device: the input of --runMode inputAlignmentsFromBAM (both of its jobs) is read into memory as it is and inflated by the functions of
+ * include/star_amd_inflate.h; the host parses the header and the record chain from the bytes that come back, and everything behind that is as with Host.
+ * Install before sah_create.  Process-wide, NULL uninstalls.  A run with Device and nothing installed fails with a text that says so. */
+typedef struct sah_inflate_fns {
+    int (*host_file)(int device, const uint8_t *fileBytes, uint64_t nBytes, staramd_inflate_result *result);
+    void (*free_result)(staramd_inflate_result *result);
+    const char *(*last_error)(void);
+} sah_inflate_fns;
+void  sah_set_inflate_device(const sah_inflate_fns *fns);
+int   sah_inflate_on_device(void *h);                                   /* 1: --gpuBAMinflate Device */
 /* chimeric detection (--chimSegmentMin > 0, --chimMultimapNmax 0, no merging of overlapping mates): the engine runs the partner loop (staramd_params::resultSelect 2)
  * instead of returning every transcript of every window.  Call before the engine contexts are created, when staramd_capabilities() has STARAMD_CAP_CHIM_SELECT;
  * returns 1 when the run's parameters now say so, 0 when they do not qualify. */

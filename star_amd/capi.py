@@ -782,6 +782,69 @@ def dedup_host(records, mark_multi=True, mate2bases_n=0):
                        records, mark_multi, mate2bases_n)
 
 
+class InflateResult(C.Structure):
+    """staramd_inflate_result (include/star_amd_inflate.h)"""
+    _fields_ = [("bytes", C.POINTER(C.c_uint8)), ("nBytes", C.c_uint64), ("nMembers", C.c_uint64), ("failedMember", C.c_int64), ("failedStatus", C.c_uint32),
+                ("stats", C.c_uint64 * 8)]
+
+
+class InflateFns(C.Structure):
+    """sah_inflate_fns (include/star_amd_host.h)"""
+    _fields_ = [("host_file", C.c_void_p), ("free_result", C.c_void_p), ("last_error", C.c_void_p)]
+
+
+class InflateDevice:
+    """include/star_amd_inflate.h: a BGZF file inflated on the MI355X (k_inflate.hip in libstaramd.so); lib_path: another library with that ABI (the wave
+    emulator's build in the CPU tests)."""
+    STATUS = ("OK", "BLOCK_TYPE", "STORED_LEN", "OVERSUBSCRIBED", "INCOMPLETE", "NO_END_CODE", "REPEAT", "SYMBOL", "DISTANCE", "INPUT_END", "OUTPUT_OVER",
+              "OUTPUT_SHORT", "STREAM_END", "CRC", "TOO_MANY")
+
+    def __init__(self, device=0, lib_path=None):
+        L = C.CDLL(lib_path or _need(ENGINE_PATH))
+        L.staramd_inflate_host_file.restype = C.c_int
+        L.staramd_inflate_host_file.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.POINTER(InflateResult)]
+        L.staramd_inflate_free.restype = None; L.staramd_inflate_free.argtypes = [C.POINTER(InflateResult)]
+        L.staramd_inflate_constant.restype = C.c_uint32; L.staramd_inflate_constant.argtypes = [C.c_int]
+        L.staramd_inflate_last_error.restype = C.c_char_p
+        self.L = L
+        self.device = device
+        self.workgroup = L.staramd_inflate_constant(0)
+        self.members_per_workgroup = L.staramd_inflate_constant(1)
+        self.workgroups_per_cu = L.staramd_inflate_constant(2)
+        self.lds_per_wavefront = L.staramd_inflate_constant(4)
+
+    def max_workgroups(self):
+        """STARAMD_INFLATE_MAX_WORKGROUPS as the next call will read it (0: not set, the default of workgroups_per_cu per CU holds)"""
+        return self.L.staramd_inflate_constant(3)
+
+    def host_file(self, data):
+        """data: the bytes of a BGZF file.  Returns (inflated bytes or None when a member failed, failedMember or -1, the status' name, nMembers, stats)"""
+        res = InflateResult()
+        buf = C.create_string_buffer(bytes(data), max(len(data), 1))
+        if self.L.staramd_inflate_host_file(self.device, buf, len(data), C.byref(res)) != 0:
+            raise RuntimeError("staramd_inflate_host_file failed: %s" % self.L.staramd_inflate_last_error().decode())
+        try:
+            failed = res.failedMember >= 0
+            out = None if failed else (C.string_at(res.bytes, res.nBytes) if res.bytes else b"")
+            return out, res.failedMember, self.STATUS[res.failedStatus], res.nMembers, list(res.stats)
+        finally:
+            self.L.staramd_inflate_free(C.byref(res))
+
+    def install(self):
+        """sah_set_inflate_device with this library's functions (process-wide).  The tool mode runs inside HostRun(): install before it"""
+        L = host_lib()
+        L.sah_set_inflate_device.restype = None; L.sah_set_inflate_device.argtypes = [C.c_void_p]
+        names = ("staramd_inflate_host_file", "staramd_inflate_free", "staramd_inflate_last_error")
+        self._fns = InflateFns(*[C.cast(getattr(self.L, n), C.c_void_p) for n in names])
+        L.sah_set_inflate_device(C.byref(self._fns))
+
+    @staticmethod
+    def uninstall():
+        L = host_lib()
+        L.sah_set_inflate_device.restype = None; L.sah_set_inflate_device.argtypes = [C.c_void_p]
+        L.sah_set_inflate_device(None)
+
+
 class device_sjdb_insertion:
     """Context manager: junction insertion (2-pass, --sjdbFileChrStartEnd / --sjdbGTFfile at the mapping stage) of every HostRun created inside
     runs through `fn_lib.fn_name` -- staramd_sjdb_insert of the engine library on a GPU box, or its plain-loop twin in the CPU tests

@@ -28,6 +28,7 @@
 #include <algorithm>
 #include "../../../include/star_amd_bgzf.h"
 #include "bgzf_resident.h"
+#include "crc32_gf2.h"                              // POLY, mulModP, xPow8: shared with k_inflate.hip
 
 namespace {
 
@@ -37,7 +38,6 @@ constexpr uint32_t NT = 256;                        // work-items per workgroup
 constexpr uint32_t HASH_BITS = 12;
 constexpr uint32_t BUF_WORDS = IN_MAX / 4;          // the block's bytes, later its deflate stream (a Huffman form only when it fits here)
 constexpr uint32_t AUX_WORDS = 1u << HASH_BITS;     // hash heads, later histograms / code tables / scan scratch
-constexpr uint32_t POLY = 0xedb88320u;              // CRC-32, reflected
 
 // aux layout once the candidates are found
 constexpr uint32_t A_LITF = 0, A_DISTF = 288, A_SCAN = 320, A_LITP = 576, A_DISTP = 864, A_SYM_L = 896, A_FRQ_L = 1184, A_SYM_D = 1472,
@@ -45,18 +45,6 @@ constexpr uint32_t A_LITF = 0, A_DISTF = 288, A_SCAN = 320, A_LITP = 576, A_DIST
                    A_SYM_C = 1960, A_FRQ_C = 1980, A_BLC_C = 2000, A_NXT_C = 2016, A_VAR = 2032;
 enum { V_DYNBITS, V_FIXBITS, V_HDRBITS, V_HLIT, V_HDIST, V_HCLEN, V_NRLE, V_MD };
 
-__device__ __forceinline__ uint32_t mulModP(uint32_t a, uint32_t b) {         // a * b mod P, reflected bit order (bit 31 = x^0)
-    uint32_t p = 0;
-#pragma unroll 1
-    for (int i = 0; i < 32; i++) { if (a & (0x80000000u >> i)) p ^= b; b = (b & 1) ? (b >> 1) ^ POLY : b >> 1; }
-    return p;
-}
-__device__ __forceinline__ uint32_t xPow8(uint32_t nBytes) {                   // x^(8 * nBytes) mod P
-    uint32_t e = nBytes * 8, p = 0x80000000u, cur = 0x40000000u;
-#pragma unroll 1
-    for (int k = 0; k < 20; k++) { if ((e >> k) & 1) p = mulModP(cur, p); cur = mulModP(cur, cur); }
-    return p;
-}
 __device__ __forceinline__ uint32_t rev(uint32_t code, uint32_t len) { return __builtin_bitreverse32(code) >> (32 - len); }
 __device__ __forceinline__ uint32_t log2u(uint32_t x) { return 31 - __clz((int)x); }
 // length 3..258 -> symbol 257..285, extra bits, extra value

@@ -63,6 +63,10 @@
 #pragma weak staramd_dedup_host_records
 #pragma weak staramd_dedup_free
 #pragma weak staramd_dedup_last_error
+// and the inflation of the tool mode's input on the device (k_inflate.hip, sah_set_inflate_device)
+#pragma weak staramd_inflate_host_file
+#pragma weak staramd_inflate_free
+#pragma weak staramd_inflate_last_error
 
 namespace {
 typedef std::chrono::steady_clock Clock;
@@ -559,6 +563,10 @@ int staramd_cli_main(int argc, char **argv, const staramd_cli_hooks *hooks, star
     if (staramd_dedup_host_records && staramd_dedup_free && staramd_dedup_last_error) {      // --gpuBAMdedup Device; likewise before sah_create
         static const sah_dedup_fns fns = {staramd_dedup_host_records, staramd_dedup_free, staramd_dedup_last_error};
         sah_set_dedup_device(&fns);
+    }
+    if (staramd_inflate_host_file && staramd_inflate_free && staramd_inflate_last_error) {      // --gpuBAMinflate Device; likewise
+        static const sah_inflate_fns fns = {staramd_inflate_host_file, staramd_inflate_free, staramd_inflate_last_error};
+        sah_set_inflate_device(&fns);
     }
     ToolBgzf toolBgzf;
     if (const int rc = toolBgzf.create(flags)) return rc;

@@ -99,7 +99,7 @@ std::string dedupFromBamFile(const RunParams &P, const std::string &bamPath, con
     BamFileInMemory bam;
     const auto t0 = std::chrono::steady_clock::now();
     auto msSince = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    std::string err = bam.load(bamPath);
+    std::string err = bam.load(P, bamPath);
     if (!err.empty()) return err;
     const double msLoad = msSince(t0);
     const auto t1 = std::chrono::steady_clock::now();

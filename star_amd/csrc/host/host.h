@@ -184,6 +184,7 @@ struct RunParams {
     std::string bamRemoveDuplicatesType = "-";          // --bamRemoveDuplicatesType - | UniqueIdentical | UniqueIdenticalNotMulti (the tool mode; alignReads ignores it, as the reference does)
     uint32_t bamRemoveDuplicatesMate2basesN = 0;        // --bamRemoveDuplicatesMate2basesN
     bool gpuDedupDevice = false;                        // --gpuBAMdedup Device: the duplicate pairs are found on the MI355X (sah_set_dedup_device)
+    bool gpuInflateDevice = false;                      // --gpuBAMinflate Device: --inputBAMfile is inflated on the MI355X (sah_set_inflate_device)
     bool runModeFromBAM = false; std::string inputBAMfile;   // --runMode inputAlignmentsFromBAM --inputBAMfile: signal tracks from an existing BAM, no mapping
     std::string varVCFfile; bool varHeteroOnly = false, wasp = false; const struct Variation *var = nullptr;   // --varVCFfile, --waspOutputMode SAMtag (Parameters.cpp:854-890)
     int readFilesSAMmates = 0;           // --readFilesType SAM SE | PE: 1 | 2 (0 = Fastx)
@@ -473,13 +474,21 @@ struct SignalDeviceParams {
 };
 std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, const std::string &sigFileName);   // --runMode inputAlignmentsFromBAM
 // a whole BAM file inflated into memory, for the two jobs of --runMode inputAlignmentsFromBAM: d = the BAM byte stream, its first headerEnd bytes the header
-// (magic, text, reference list) as read; recs = every whole record (at its block_size word), in the file's order.  load: error text or ""
+// (magic, text, reference list) as read; recs = every whole record (at its block_size word), in the file's order.  load: error text or "".  The file is
+// inflated by gzread (--gpuBAMinflate Host) or, member by member, by the installed functions of include/star_amd_inflate.h (Device); one Log.out line says which
 struct BamFileInMemory {
     std::vector<char> d; size_t headerEnd = 0;
     std::vector<std::string> chrName; std::vector<uint64_t> chrLength;
     std::vector<const char *> recs;
-    std::string load(const std::string &bamPath);
+    std::string load(const RunParams &P, const std::string &bamPath);
+private:
+    std::string inflateOnHost(const std::string &bamPath, uint64_t &nMembers, uint64_t &nIn);
+    std::string inflateOnDevice(const RunParams &P, const std::string &bamPath, uint64_t &nMembers, uint64_t &nIn);
 };
+// the functions behind --gpuBAMinflate Device (sah_set_inflate_device; nullptr while none is installed)
+void setInflateDeviceFns(const ::sah_inflate_fns *fns);
+const ::sah_inflate_fns *inflateDeviceFns();
+inline constexpr const char *INFLATE_DEVICE_MISSING = "EXITING because of fatal PARAMETERS error: --gpuBAMinflate Device, but no device inflate functions are installed (sah_set_inflate_device)";
 
 // ---- dedup.cpp: --bamRemoveDuplicatesType in the tool mode (source/bamRemoveDuplicates.cpp; the rule: DESIGN.md 7.6, star_amd/csrc/dedup_rule.h)
 // the functions behind --gpuBAMdedup Device (sah_set_dedup_device; nullptr while none is installed)

@@ -284,6 +284,7 @@ std::string RunParams::parse(int argc, char **argv) {
         else if (k == "gpuBAMsort") { const std::string &s = one(k, v); if (s == "Device") gpuBAMsortDevice = true; else if (s == "Host") gpuBAMsortDevice = false; else err = "EXITING: --gpuBAMsort takes Host or Device"; }
         else if (k == "gpuBAMsortHBM") gpuBAMsortHBM = (uint64_t)U(k, v);
         else if (k == "gpuSignal") { const std::string &s = one(k, v); if (s == "Device") gpuSignalDevice = true; else if (s == "Host") gpuSignalDevice = false; else err = "EXITING: --gpuSignal takes Host or Device"; }
+        else if (k == "gpuBAMinflate") { const std::string &s = one(k, v); if (s == "Device") gpuInflateDevice = true; else if (s == "Host") gpuInflateDevice = false; else err = "EXITING: --gpuBAMinflate takes Host or Device"; }
         else if (k == "gpuBAMdedup") { const std::string &s = one(k, v); if (s == "Device") gpuDedupDevice = true; else if (s == "Host") gpuDedupDevice = false; else err = "EXITING: --gpuBAMdedup takes Host or Device"; }
         else if (k == "bamRemoveDuplicatesType") {      // Parameters.cpp:565-580
             bamRemoveDuplicatesType = one(k, v);

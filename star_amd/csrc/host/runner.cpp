@@ -718,6 +718,8 @@ void sah_set_signal_device(const sah_signal_fns *fns) { staramd::setSignalDevice
 int sah_signal_on_device(void *h) { return ((Runner *)h)->P.gpuSignalDevice ? 1 : 0; }
 void sah_signal_counts(void *h, uint64_t out[8]) { for (int i = 0; i < 8; i++) out[i] = ((Runner *)h)->sorted.signalCounts[i]; }
 void sah_set_dedup_device(const sah_dedup_fns *fns) { staramd::setDedupDeviceFns(fns); }
+void sah_set_inflate_device(const sah_inflate_fns *fns) { staramd::setInflateDeviceFns(fns); }
+int sah_inflate_on_device(void *h) { return ((Runner *)h)->P.gpuInflateDevice ? 1 : 0; }
 int sah_dedup_on_device(void *h) { return ((Runner *)h)->P.gpuDedupDevice ? 1 : 0; }
 void sah_dedup_counts(void *h, uint64_t out[8]) { for (int i = 0; i < 8; i++) out[i] = ((Runner *)h)->dedupCounts[i]; }
 int sah_dedup_host_records(const staramd_dedup_params *params, const uint8_t *bytes, uint64_t nBytes, const uint64_t *offsets, uint64_t n, staramd_dedup_result *result) {

@@ -5,6 +5,8 @@
 #include "host.h"
 #include <cstring>
 #include <cstdio>
+#include <cstdlib>
+#include <chrono>
 #include <zlib.h>
 
 namespace staramd {
@@ -205,7 +207,11 @@ std::string signalFromRuns(const RunParams &P, const std::vector<std::string> &c
 
 // The input of --runMode inputAlignmentsFromBAM, for both of its jobs (the tracks below, the duplicate marking of dedup.cpp): the file is inflated block by
 // block (BGZF = concatenated gzip members) and held in memory; chromosome names and lengths come from its header.
-std::string BamFileInMemory::load(const std::string &bamPath) {
+static sah_inflate_fns g_inflateFns = {nullptr, nullptr, nullptr};
+void setInflateDeviceFns(const sah_inflate_fns *fns) { if (fns) g_inflateFns = *fns; else g_inflateFns = {nullptr, nullptr, nullptr}; }
+const sah_inflate_fns *inflateDeviceFns() { return g_inflateFns.host_file && g_inflateFns.free_result && g_inflateFns.last_error ? &g_inflateFns : nullptr; }
+
+std::string BamFileInMemory::inflateOnHost(const std::string &bamPath, uint64_t &nMembers, uint64_t &nIn) {
     gzFile in = gzopen(bamPath.c_str(), "rb");
     if (!in) return "EXITING because of fatal INPUT error: could not open --inputBAMfile " + bamPath;
     for (;;) {
@@ -216,7 +222,54 @@ std::string BamFileInMemory::load(const std::string &bamPath) {
         d.resize(old + (size_t)got);
         if ((size_t)got < block) break;
     }
+    const z_off_t at = gzoffset(in);                            // (compressed bytes read; gzread does not count members)
+    nIn = at > 0 ? (uint64_t)at : 0; nMembers = 0;
     gzclose(in);
+    return "";
+}
+// --gpuBAMinflate Device: the file as it is goes to the installed functions, the inflated bytes come back
+std::string BamFileInMemory::inflateOnDevice(const RunParams &P, const std::string &bamPath, uint64_t &nMembers, uint64_t &nIn) {
+    const sah_inflate_fns *fns = inflateDeviceFns();
+    if (!fns) return INFLATE_DEVICE_MISSING;
+    const bool timing = getenv("STARAMD_HOST_TIMING") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+    std::vector<uint8_t> file;
+    FILE *f = fopen(bamPath.c_str(), "rb");
+    if (!f) return "EXITING because of fatal INPUT error: could not open --inputBAMfile " + bamPath;
+    for (;;) {
+        const size_t old = file.size(), block = 1u << 24;
+        file.resize(old + block);
+        const size_t got = fread(file.data() + old, 1, block, f);
+        file.resize(old + got);
+        if (got < block) break;
+    }
+    const bool readFailed = ferror(f) != 0;
+    fclose(f);
+    if (readFailed) return "EXITING because of fatal INPUT error: could not read --inputBAMfile " + bamPath;
+    const double msRead = ms();
+    staramd_inflate_result res;
+    if (fns->host_file(P.gpuDevice, file.data(), file.size(), &res)) return deviceError("--gpuBAMinflate", fns->last_error());
+    const double msDevice = ms() - msRead;
+    nMembers = res.nMembers; nIn = file.size();
+    if (res.failedMember >= 0) { fns->free_result(&res); return "EXITING because of fatal INPUT error: could not decompress --inputBAMfile " + bamPath; }
+    if (res.nBytes) d.assign((const char *)res.bytes, (const char *)res.bytes + res.nBytes);
+    fns->free_result(&res);
+    if (timing) fprintf(stderr, "  inflate stage (device): file read %.2f ms, walk + device %.2f ms, copy into place %.2f ms\n", msRead, msDevice, ms() - msRead - msDevice);
+    return "";
+}
+
+std::string BamFileInMemory::load(const RunParams &P, const std::string &bamPath) {
+    uint64_t nMembers = 0, nIn = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::string inflErr = P.gpuInflateDevice ? inflateOnDevice(P, bamPath, nMembers, nIn) : inflateOnHost(bamPath, nMembers, nIn);
+    if (!inflErr.empty()) return inflErr;
+    const double msInflate = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (P.gpuInflateDevice) appendLog(P.outFileNamePrefix + "Log.out", "--inputBAMfile inflated on the Device (--gpuBAMinflate): %llu members, %llu bytes in, %llu bytes out\n", (unsigned long long)nMembers, (unsigned long long)nIn, (unsigned long long)d.size());
+    else appendLog(P.outFileNamePrefix + "Log.out", "--inputBAMfile inflated on the Host (--gpuBAMinflate): %llu bytes in, %llu bytes out\n", (unsigned long long)nIn, (unsigned long long)d.size());
+    const auto t1 = std::chrono::steady_clock::now();
+    struct ParseTime { bool on; double msInflate; std::chrono::steady_clock::time_point t1; ~ParseTime() { if (on) fprintf(stderr, "  load: inflate %.2f ms, header and record parse %.2f ms\n", msInflate, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count()); } }
+        parseTime{getenv("STARAMD_HOST_TIMING") != nullptr, msInflate, t1};
     if (d.size() < 12 || memcmp(d.data(), "BAM\1", 4) != 0) return "EXITING because of fatal INPUT error: --inputBAMfile " + bamPath + " is not a BAM file";
     size_t p = 8 + rd32(d.data() + 4);
     if (p + 4 > d.size()) return "EXITING because of fatal INPUT error: truncated BAM header in " + bamPath;
@@ -241,7 +294,7 @@ std::string BamFileInMemory::load(const std::string &bamPath) {
 // --runMode inputAlignmentsFromBAM --inputBAMfile x.bam --outWigType ... (Parameters.cpp:585-592): the same tracks from a coordinate-sorted BAM file.
 std::string signalFromBamFile(const RunParams &P, const std::string &bamPath, const std::string &sigFileName) {
     BamFileInMemory bam;
-    const std::string loadErr = bam.load(bamPath);
+    const std::string loadErr = bam.load(P, bamPath);
     if (!loadErr.empty()) return loadErr;
     const std::vector<char> &d = bam.d;
     const std::vector<std::string> &chrName = bam.chrName; const std::vector<uint64_t> &chrLength = bam.chrLength;
