@@ -11,6 +11,7 @@ HIPFLAGS := --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-un
 # k_stitch.hip is compiled without loop unrolling (round 2: fewer spills, 3 % faster; round 5: 106 VGPRs, no scratch -- tools/isa_stats.sh k_stitch says which of the
 # register allocator's two regimes a build is in, tests/test_isa_static.py notices a flip); the other kernels keep the default
 STITCH_WAVES ?= 4
+EMUL_CXX ?= /opt/rocm/lib/llvm/bin/clang++
 STITCH_FLAGS := -fno-unroll-loops -DSTITCH_WAVES=$(STITCH_WAVES)
 
 # $(call build_engine,<variant>,<extra defines>): every .hip file to its own object (in parallel), then one shared library
@@ -34,9 +35,9 @@ all: host engine shadow cli oracle
 host: star_amd/lib/libstaramd_host.so
 engine: star_amd/lib/libstaramd.so
 cli: star_amd/bin/star_amd star_amd/lib/libstaramd_cli.so
-oracle: oracle/_build/liboracle.so oracle/_build/libindex_emul.so oracle/_build/star_amd_oracle_cli oracle/_build/libstaramd_cli_oracle.so oracle/_build/libstaramd_cli_replay.so oracle/_build/libstaramd_emul.so oracle/_build/star_amd_emul_cli oracle/_build/libstaramd_units_emul.so
+oracle: oracle/_build/liboracle.so oracle/_build/libindex_emul.so oracle/_build/star_amd_oracle_cli oracle/_build/libstaramd_cli_oracle.so oracle/_build/libstaramd_cli_replay.so oracle/_build/libstaramd_emul.so oracle/_build/star_amd_emul_cli oracle/_build/libstaramd_units_emul.so oracle/_build/libseq_emul.so oracle/_build/seq_insert_check oracle/_build/seq_insert_gpu
 
-star_amd/lib/libstaramd_host.so: $(HOST_LIB_SRC) star_amd/csrc/host/host.h star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_index.h include/star_amd_host.h include/star_amd_bgzf.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_dedup.h include/star_amd_inflate.h star_amd/csrc/bam_aux.h star_amd/csrc/dedup_rule.h
+star_amd/lib/libstaramd_host.so: $(HOST_LIB_SRC) star_amd/csrc/host/host.h star_amd/csrc/chim_pair.h include/star_amd.h include/star_amd_index.h include/star_amd_host.h include/star_amd_bgzf.h include/star_amd_bamsort.h include/star_amd_signal.h include/star_amd_dedup.h include/star_amd_inflate.h star_amd/csrc/bam_aux.h star_amd/csrc/dedup_rule.h $(wildcard star_amd/csrc/index/*.h)
 	@mkdir -p star_amd/lib
 	$(CXX) $(CXXFLAGS) -shared $(HOST_LIB_SRC) -o $@ -lz
 
@@ -65,6 +66,19 @@ oracle/_build/liboracle.so: oracle/star_oracle.cpp include/star_amd.h
 oracle/_build/libindex_emul.so: oracle/index_emul.cpp oracle/loop_backend.h $(wildcard star_amd/csrc/index/*.h)
 	@mkdir -p oracle/_build
 	$(CXX) $(CXXFLAGS) -fopenmp -shared oracle/index_emul.cpp -o $@
+
+# test infrastructure: the sequence insertion (star_amd/csrc/index/seq_core.h) on the plain-loop backend behind the signature of staramd_seq_insert
+# (tests/test_seq_insert.py), and its routine checks: the plain-loop one and the gfx950 one (tests/test_seq_insert_routines.py, tests/test_gpu_seq_insert_routines.py)
+SEQ_CHECK_HDR := tests/seq_insert_cases.h oracle/index_routines_cases.h oracle/loop_backend.h $(wildcard star_amd/csrc/index/*.h)
+oracle/_build/libseq_emul.so: tests/seq_insert_emul.cpp oracle/loop_backend.h $(wildcard star_amd/csrc/index/*.h) include/star_amd_index.h
+	@mkdir -p oracle/_build
+	$(CXX) $(CXXFLAGS) -fopenmp -shared tests/seq_insert_emul.cpp -o $@
+oracle/_build/seq_insert_check: tests/seq_insert_check.cpp $(SEQ_CHECK_HDR)
+	@mkdir -p oracle/_build
+	$(EMUL_CXX) -x c++ -std=c++17 -O2 -Wno-unknown-attributes -Wno-unused-result tests/seq_insert_check.cpp -o $@
+oracle/_build/seq_insert_gpu: tests/seq_insert_gpu.hip $(SEQ_CHECK_HDR)
+	@mkdir -p oracle/_build
+	$(HIPCC) $(HIPFLAGS) tests/seq_insert_gpu.hip -o $@
 
 # test infrastructure: the command-line front end with the oracle behind the engine's C ABI (oracle/cli_shim.cpp), for CPU tests of main.cpp
 oracle/_build/star_amd_oracle_cli: $(CLI_SRC) oracle/cli_shim.cpp oracle/_build/liboracle.so oracle/_build/libindex_emul.so star_amd/lib/libstaramd_host.so $(CLI_HDR)
@@ -103,7 +117,6 @@ oracle/_build/star_amd_emul_cli: $(CLI_SRC) oracle/_build/libstaramd_emul.so sta
 # the five stand-alone device units (k_bgzf, k_bamsort, k_signal, k_dedup, k_inflate) compiled for the host by the wavefront emulator, with its runtime: what the CPU
 # tests of these units build for themselves in a temporary folder (tests/util.py, tests/test_dedup_emul.py); here so that `make` says when a unit stops compiling
 UNITS_EMUL := k_bgzf k_bamsort k_signal k_dedup k_inflate
-EMUL_CXX ?= /opt/rocm/lib/llvm/bin/clang++
 oracle/_build/libstaramd_units_emul.so: $(foreach u,$(UNITS_EMUL),star_amd/csrc/engine/$(u).hip) $(HIP_HDR) $(wildcard oracle/wave_emul/*.cpp oracle/wave_emul/*.h oracle/wave_emul/hip/*.h oracle/wave_emul/rocprim/*.hpp)
 	@mkdir -p oracle/_build/units_emul
 	@rm -f oracle/_build/units_emul/*.o

@@ -36,6 +36,9 @@ int   sah_tool_done(void *h);                                           /* 1: --
  * (star_amd_index.h), then sah_generate_finish inserts the annotated junctions and writes the genomeDir files */
 /* call BEFORE sah_create: junction insertion runs on the device through fn (= staramd_sjdb_insert); NULL = host restatement (sjdb_insert.cpp) */
 void  sah_set_sjdb_device_fn(int (*fn)(int device, const staramd_sjdb_args *, staramd_sjdb_result *), int device);
+/* call BEFORE sah_create: --genomeFastaFiles at the mapping stage inserts the added sequences through fn (= staramd_seq_insert of star_amd_index.h) on
+ * `device`; process-wide, NULL uninstalls.  There is no host restatement: a run with --genomeFastaFiles and no fn installed ends with a text that says so. */
+void  sah_set_seq_insert_fn(int (*fn)(int device, const staramd_seq_args *, staramd_seq_result *), int device);
 /* junction insertion on the arrays RESIDENT in the engine contexts: fn runs staramd_insert_junctions on every context (include/star_amd.h);
  * used once sah_engines_ready was called; sah_index_in_engine: 1 = the last phase change left the new index in the engines already
  * (follow with staramd_update_tables instead of staramd_update_index); reading it clears it */

@@ -60,6 +60,28 @@ typedef struct staramd_sjdb_args {
 typedef struct staramd_sjdb_result { uint64_t nInd, nSAnew, nSAbyteNew, nSAibyte; float msTotal; uint32_t reserved; } staramd_sjdb_result;
 int staramd_sjdb_insert(int device, const staramd_sjdb_args *a, staramd_sjdb_result *res);
 
+/* Extra reference sequences added to a finished index (--genomeFastaFiles at the mapping stage: Genome::insertSequences + insertSeqSA,
+ * source/Genome_insertSequences.cpp:9-33, source/insertSeqSA.cpp:18-319) on the device, host buffers in and out: the search of every suffix of the
+ * added text in the old suffix array, their order, the merge (old entries re-based on the way) and the SAindex of the result.
+ *   G         old genome text: nGenomeReal bytes of chromosomes, then the junction block up to nGenomeOld
+ *   Gins      the added text, nGins codes: sequences padded with spacers (5) to 2^genomeChrBinNbits, as genomeScanFastaFiles lays them out
+ * The new genome text is G[0, nGenomeReal) + Gins + G[nGenomeReal, nGenomeOld): the caller assembles its own copy.
+ * SAout / SAiOut are sized by the caller: nSAnew = nSAold + 2 * (number of codes < 4 in Gins).
+ * Returns 0, STARAMD_ERR_RESULT_OVERFLOW (capacity), STARAMD_ERR_ARG (bad first suffix, or the reference's GstrandBit error: the text of
+ * staramd_index_last_error says which), STARAMD_ERR_DEVICE. */
+typedef struct staramd_seq_args {
+    const uint8_t *G; uint64_t nGenomeOld, nGenomeReal;
+    const uint8_t *SA; uint64_t nSAold, nSAbyteOld; uint32_t GstrandBit, gSAindexNbases;
+    const uint8_t *Gins; uint64_t nGins;
+    uint8_t *SAout; uint64_t saOutCapacity; uint8_t *SAiOut; uint64_t saiOutCapacity;
+} staramd_seq_args;
+typedef struct staramd_seq_result {
+    uint64_t nInd, nSAnew, nSAbyteNew, nSAibyte;
+    uint64_t nCapHits;         /* searches that compared 10000 characters without a difference (suffixArraySearch1's N) */
+    uint32_t doublingRounds; float msTotal;
+} staramd_seq_result;
+int staramd_seq_insert(int device, const staramd_seq_args *a, staramd_seq_result *res);
+
 const char *staramd_index_last_error(void);
 
 #ifdef __cplusplus

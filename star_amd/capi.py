@@ -866,6 +866,27 @@ class device_sjdb_insertion:
         return False
 
 
+class device_seq_insertion:
+    """Context manager: the sequences that --genomeFastaFiles adds at the mapping stage are inserted, for every HostRun created inside, through
+    `fn_lib.fn_name` -- staramd_seq_insert of the engine library on a GPU box, or its plain-loop twin in the CPU tests
+    (oracle/_build/libseq_emul.so: seq_emul_insert).  Process-wide switch of the host library; there is no host restatement behind it."""
+
+    def __init__(self, lib_path=None, fn_name="staramd_seq_insert", device=0):
+        self.lib = C.CDLL(lib_path or _need(ENGINE_PATH))
+        self.fn = C.cast(getattr(self.lib, fn_name), C.c_void_p)
+        self.device = device
+
+    def __enter__(self):
+        L = host_lib()
+        L.sah_set_seq_insert_fn.restype = None; L.sah_set_seq_insert_fn.argtypes = [C.c_void_p, C.c_int]
+        L.sah_set_seq_insert_fn(self.fn, self.device)
+        return self
+
+    def __exit__(self, *a):
+        host_lib().sah_set_seq_insert_fn(None, 0)
+        return False
+
+
 # ---- the command-line front end as a function (include/star_amd_cli.h) ----
 
 class CliHooks(C.Structure):

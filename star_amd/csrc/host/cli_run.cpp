@@ -67,6 +67,8 @@
 #pragma weak staramd_inflate_host_file
 #pragma weak staramd_inflate_free
 #pragma weak staramd_inflate_last_error
+// and the insertion of added reference sequences (index_gpu.hip, sah_set_seq_insert_fn): a run with --genomeFastaFiles there ends with the text that says so
+#pragma weak staramd_seq_insert
 
 namespace {
 typedef std::chrono::steady_clock Clock;
@@ -556,6 +558,7 @@ int staramd_cli_main(int argc, char **argv, const staramd_cli_hooks *hooks, star
     for (int i = 1; i < argc; i++) if (std::string(argv[i]) == "--version") { printf("2.7.11b\n"); return 0; }      // the version whose behaviour is reproduced (Parameters.cpp:340-343)
     CliFlags flags = splitFlags(argc, argv);
     if (!getenv("STARAMD_SJDB_HOST")) sah_set_sjdb_device_fn(staramd_sjdb_insert, flags.devices.empty() ? 0 : flags.devices[0]);   // junction insertion on the device
+    if (staramd_seq_insert) sah_set_seq_insert_fn(staramd_seq_insert, flags.devices.empty() ? 0 : flags.devices[0]);      // --genomeFastaFiles at the mapping stage; before sah_create, where the index is loaded
     if (staramd_signal_host_records && staramd_bamsort_finish_signal && staramd_signal_free && staramd_signal_last_error) {      // --gpuSignal Device; before sah_create, where the tool mode runs
         static const sah_signal_fns fns = {staramd_signal_host_records, staramd_bamsort_finish_signal, staramd_signal_free, staramd_signal_last_error};
         sah_set_signal_device(&fns);

@@ -15,24 +15,15 @@ static inline uint8_t ntCode(unsigned char c) {          // convertNucleotidesTo
     switch (c) { case 'A': case 'a': return 0; case 'C': case 'c': return 1; case 'G': case 'g': return 2; case 'T': case 't': return 3; default: return 4; }
 }
 
-std::string genomeGenerateScan(RunParams &P, GenomeIndex &gi, GenerateJob &job) {
-    gi.dir = P.genomeDir;
-    memset(&gi.view, 0, sizeof(gi.view));
-    if (P.genomeSAsparseD != 1) return "EXITING because of fatal PARAMETERS error: --genomeSAsparseD " + std::to_string(P.genomeSAsparseD) + ": only 1 is built on the MI355X (use the reference for sparse suffix arrays)";
-    // createDirectory(pGe.gDir, ...) (:101)
-    if (mkdir(P.genomeDir.c_str(), S_IRWXU | S_IRGRP | S_IXGRP | S_IROTH | S_IXOTH) != 0 && errno != EEXIST) {
-        std::string perr = P.genomeDir;
-        for (size_t i = perr.find('/', 1); i != std::string::npos; i = perr.find('/', i + 1)) mkdir(perr.substr(0, i).c_str(), S_IRWXU | S_IRGRP | S_IXGRP | S_IROTH | S_IXOTH);
-        if (mkdir(P.genomeDir.c_str(), S_IRWXU | S_IRGRP | S_IXGRP | S_IROTH | S_IXOTH) != 0 && errno != EEXIST)
-            return "EXITING because of fatal ERROR: could not create output directory: " + P.genomeDir + " for --genomeDir";
-    }
-    const uint64_t binBases = 1ull << P.genomeChrBinNbits;
+// genomeScanFastaFiles (genomeScanFastaFiles.cpp:5-92) from N = 0: codes into G, every sequence padded with spacers to a bin boundary; names, lengths and
+// starts (one more entry: the padded end) of the sequences.  Shared by genomeGenerate and by --genomeFastaFiles at the mapping stage (GenomeIndex::insertSequences)
+std::string scanFastaFiles(const std::vector<std::string> &files, uint64_t binBases, std::vector<uint8_t> &G, std::vector<std::string> &chrName,
+                           std::vector<uint64_t> &chrStart, std::vector<uint64_t> &chrLength) {
     // genomeScanFastaFiles: chromosomes padded to bin boundaries with at least one spacer (:47-49, :74)
-    std::vector<uint8_t> &G = gi.G;
     G.clear();
-    gi.chrName.clear(); gi.chrStart.clear(); gi.chrLength.clear();
+    chrName.clear(); chrStart.clear(); chrLength.clear();
     uint64_t N = 0;
-    for (const std::string &fa : P.genomeFastaFiles) {
+    for (const std::string &fa : files) {
         FILE *f = fopen(fa.c_str(), "rb");
         if (!f) return "EXITING because of INPUT ERROR: could not open genomeFastaFile: " + fa + "\n";
         std::vector<char> buf(1 << 24);
@@ -50,10 +41,10 @@ std::string genomeGenerateScan(RunParams &P, GenomeIndex &gi, GenerateJob &job) 
                         inHeader = false; lineStart = true;
                         std::istringstream ls(header); ls.ignore(1, ' ');
                         std::string name; ls >> name;
-                        gi.chrName.push_back(name);
-                        if (!gi.chrStart.empty()) gi.chrLength.push_back(N - gi.chrStart.back());
+                        chrName.push_back(name);
+                        if (!chrStart.empty()) chrLength.push_back(N - chrStart.back());
                         if (N > 0) N = ((N + 1) / binBases + 1) * binBases;
-                        gi.chrStart.push_back(N);
+                        chrStart.push_back(N);
                         if (G.size() < N) G.resize(N, 5);
                     } else header.push_back((char)c);
                     continue;
@@ -69,12 +60,33 @@ std::string genomeGenerateScan(RunParams &P, GenomeIndex &gi, GenerateJob &job) 
         if (first) return "EXITING because of INPUT ERROR: could not read from genomeFastaFile: " + fa + "\n";
         if (inHeader) return "EXITING because of INPUT ERROR: genomeFastaFile ends inside a header line: " + fa + "\n";
     }
-    if (gi.chrStart.empty()) return "EXITING because of INPUT ERROR: no sequences in --genomeFastaFiles";
-    gi.chrLength.push_back(N - gi.chrStart.back());
+    if (chrStart.empty()) return "EXITING because of INPUT ERROR: no sequences in --genomeFastaFiles";
+    chrLength.push_back(N - chrStart.back());
     N = ((N + 1) / binBases + 1) * binBases;
     G.resize(N, 5);
+    chrStart.push_back(N);
+    return "";
+}
+
+std::string genomeGenerateScan(RunParams &P, GenomeIndex &gi, GenerateJob &job) {
+    gi.dir = P.genomeDir;
+    memset(&gi.view, 0, sizeof(gi.view));
+    if (P.genomeSAsparseD != 1) return "EXITING because of fatal PARAMETERS error: --genomeSAsparseD " + std::to_string(P.genomeSAsparseD) + ": only 1 is built on the MI355X (use the reference for sparse suffix arrays)";
+    // createDirectory(pGe.gDir, ...) (:101)
+    if (mkdir(P.genomeDir.c_str(), S_IRWXU | S_IRGRP | S_IXGRP | S_IROTH | S_IXOTH) != 0 && errno != EEXIST) {
+        std::string perr = P.genomeDir;
+        for (size_t i = perr.find('/', 1); i != std::string::npos; i = perr.find('/', i + 1)) mkdir(perr.substr(0, i).c_str(), S_IRWXU | S_IRGRP | S_IXGRP | S_IROTH | S_IXOTH);
+        if (mkdir(P.genomeDir.c_str(), S_IRWXU | S_IRGRP | S_IXGRP | S_IROTH | S_IXOTH) != 0 && errno != EEXIST)
+            return "EXITING because of fatal ERROR: could not create output directory: " + P.genomeDir + " for --genomeDir";
+    }
+    const uint64_t binBases = 1ull << P.genomeChrBinNbits;
+    {
+        const std::string e = scanFastaFiles(P.genomeFastaFiles, binBases, gi.G, gi.chrName, gi.chrStart, gi.chrLength);
+        if (!e.empty()) return e;
+    }
+    std::vector<uint8_t> &G = gi.G;
+    const uint64_t N = G.size();
     const uint32_t nChr = (uint32_t)gi.chrName.size();
-    gi.chrStart.push_back(N);
     // writeChrInfo (:418-432)
     {
         std::ofstream chrN(P.genomeDir + "/chrName.txt"), chrS(P.genomeDir + "/chrStart.txt"), chrL(P.genomeDir + "/chrLength.txt"), chrNL(P.genomeDir + "/chrNameLength.txt");

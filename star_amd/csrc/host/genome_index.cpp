@@ -2,6 +2,7 @@
 // Follows Genome::genomeLoad (source/Genome_genomeLoad.cpp:18-467), Genome::chrInfoLoad / chrBinFill
 // (source/Genome.cpp:139-215) and Genome::loadSJDB (source/Genome_genomeLoad.cpp:471-521).
 #include "host.h"
+#include "../index/seq_core.h"
 #include <fstream>
 #include <sstream>
 #include <cmath>
@@ -96,6 +97,7 @@ std::string GenomeIndex::load(const std::string &genomeDir) {
     view.GstrandBit = GstrandBit; view.gSAindexNbases = gSAindexNbases; view.gSAsparseD = gSAsparseD;
     view.gChrBinNbits = gChrBinNbits;
     view.chrStart = chrStart.data(); view.chrLength = chrLength.data(); view.nChrReal = nChrReal;
+    insertChrIndFirst = nChrReal;        // Genome_genomeLoad.cpp:246
     // --- chrBinFill (Genome.cpp:209-215)
     uint64_t binBases = 1ull << gChrBinNbits;
     uint64_t chrBinN = chrStart[nChrReal] / binBases + 1;
@@ -131,6 +133,59 @@ std::string GenomeIndex::load(const std::string &genomeDir) {
         view.sjdbMotif = sjdbMotif.data(); view.sjdbShiftLeft = sjdbShiftLeft.data(); view.sjdbShiftRight = sjdbShiftRight.data(); view.sjdbStrand = sjdbStrand.data();
     }
     loadSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return "";
+}
+
+// ---- --genomeFastaFiles at the mapping stage (Genome::insertSequences, source/Genome_insertSequences.cpp:9-33; sizes: Genome_genomeLoad.cpp:244-250)
+static SeqInsertFn g_seqInsertFn = nullptr; static int g_seqInsertDevice = 0;
+void setSeqInsertFn(SeqInsertFn fn, int device) { g_seqInsertFn = fn; g_seqInsertDevice = device; }
+
+std::string GenomeIndex::insertSequences(const RunParams &P, std::string &log) {
+    if (!g_seqInsertFn) return SEQ_INSERT_MISSING;
+    const uint32_t nChrOld = view.nChrReal;
+    const uint64_t binBases = 1ull << view.gChrBinNbits, nG = chrStart[nChrOld], nGenomeOld = G.size();
+    // the added text as genomeScanFastaFiles lays it out behind the last chromosome: nG is a bin boundary, so offsets from 0 are offsets from nG
+    std::vector<uint8_t> G1; std::vector<std::string> names; std::vector<uint64_t> starts, lengths;
+    {
+        const std::string e = scanFastaFiles(P.genomeFastaFiles, binBases, G1, names, starts, lengths);
+        if (!e.empty()) return e;
+    }
+    const uint64_t nG1 = G1.size();
+    if (staridx::seqStrandBitCheck(nG, nG1, view.GstrandBit + 1)) return staridx::SEQ_STRANDBIT_ERROR;      // insertSeqSA.cpp:21-29
+    log += " ..... inserting extra sequences into genome indexes\n";
+    uint64_t nInd = 0;
+    for (uint8_t c : G1) nInd += c < 4;
+    nInd *= 2;
+    const uint32_t wSA = view.GstrandBit + 1;
+    const uint64_t nSAnew = view.nSA + nInd;
+    std::vector<uint8_t> SAnew(staridx::packedBytes(nSAnew + 1, wSA) + 16, 0), SAiNew(view.nSAibyte + 24, 0);
+    staramd_seq_args a; memset(&a, 0, sizeof(a));
+    a.G = G.data(); a.nGenomeOld = nGenomeOld; a.nGenomeReal = nG;
+    a.SA = SA.data(); a.nSAold = view.nSA; a.nSAbyteOld = view.nSAbyte; a.GstrandBit = view.GstrandBit; a.gSAindexNbases = view.gSAindexNbases;
+    a.Gins = G1.data(); a.nGins = nG1;
+    a.SAout = SAnew.data(); a.saOutCapacity = SAnew.size(); a.SAiOut = SAiNew.data(); a.saiOutCapacity = SAiNew.size();
+    staramd_seq_result r; memset(&r, 0, sizeof(r));
+    const int rc = g_seqInsertFn(g_seqInsertDevice, &a, &r);
+    if (rc) return "EXITING because of FATAL ERROR: sequence insertion on the MI355X failed (code " + std::to_string(rc) + ")";
+    if (r.nInd != nInd || r.nSAibyte != view.nSAibyte) return "EXITING because of FATAL ERROR: sequence insertion on the MI355X returned an index of unexpected size";
+    log += "   Finished SA search, number of new SA indices = " + std::to_string(nInd) + "\n   Finished inserting SA indices\n";
+    { char t[200]; snprintf(t, sizeof t, "star_amd: sequence insertion on the device: %.1f ms, %u doubling rounds, %llu searches stopped at 10000 characters\n", (double)r.msTotal, r.doublingRounds, (unsigned long long)r.nCapHits); log += t; }
+    // the new index: chromosomes, added sequences, the moved junction block (:19-25)
+    G.insert(G.begin() + nG, G1.begin(), G1.end());
+    SAnew.resize(staridx::packedBytes(nSAnew, wSA) + 8); SA.swap(SAnew);
+    SAiNew.resize(view.nSAibyte + 8); SAi.swap(SAiNew);
+    chrStart.pop_back();
+    for (size_t i = 0; i < names.size(); i++) { chrName.push_back(names[i]); chrStart.push_back(nG + starts[i]); chrLength.push_back(lengths[i]); }
+    chrStart.push_back(nG + nG1);
+    const uint32_t nChr = (uint32_t)chrName.size();
+    view.nChrReal = nChr; view.nSA = nSAnew; view.nSAbyte = staridx::packedBytes(nSAnew, wSA);
+    view.sjGstart = view.sjdbN == 0 ? chrStart[nChr] + 1 : chrStart[nChr];
+    const uint64_t chrBinN = chrStart[nChr] / binBases + 1;      // chrBinFill (Genome.cpp:209-215)
+    chrBin.assign(chrBinN, 0);
+    for (uint64_t ii = 0, ichr = 1; ii < chrBinN; ++ii) { if (ii * binBases >= chrStart[ichr]) ichr++; chrBin[ii] = (uint32_t)(ichr - 1); }
+    view.chrBinN = chrBinN;
+    seqInserted = true;
+    refreshView();
     return "";
 }
 

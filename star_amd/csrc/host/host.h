@@ -68,11 +68,16 @@ struct GenomeIndex {
     staramd_genome view;      // pointers into the vectors above
     double loadSeconds = 0;
     bool sjdbInfoExists = false;
+    uint32_t insertChrIndFirst = 0;  // genomeInsertChrIndFirst: number of chromosomes of the index on disk; those added with --genomeFastaFiles at the mapping stage follow
+    bool seqInserted = false;        // sequences were added: --sjdbInsertSave All writes the chromosome tables of the NEW index
     bool engineHoldsIndex = false;   // set by the front end once every engine context holds this index (staramd_create): insertion may then run on the resident arrays
     bool indexInEngine = false;      // the last junction insertion ran on the resident arrays: the engines need staramd_update_tables, not a re-upload
     // returns empty string on success, else the error text
     std::string load(const std::string &genomeDir);
     void refreshView();       // re-point `view` at the vectors after they were rewritten (sjdb insertion)
+    // --genomeFastaFiles at the mapping stage (Genome::insertSequences): scans the files, appends the chromosomes, moves the junction block behind them and
+    // inserts their suffixes through the function of setSeqInsertFn; `log` gets the reference's Log.out lines
+    std::string insertSequences(const struct RunParams &P, std::string &log);
     // names and lengths of the real chromosomes (the first view.nChrReal entries; junction inserts follow), as the signal writers take them
     std::vector<std::string> realChrNames() const { return std::vector<std::string>(chrName.begin(), chrName.begin() + view.nChrReal); }
     std::vector<uint64_t> realChrLengths() const { return std::vector<uint64_t>(chrLength.begin(), chrLength.begin() + view.nChrReal); }
@@ -180,6 +185,8 @@ struct RunParams {
     std::vector<std::string> outSAMheaderHD, outSAMheaderPG; std::string outSAMheaderCommentFile;   // samHeaders.cpp:56-96
     bool runDirPermAll = false, genomeLoadShared = false;
     // --runMode genomeGenerate (genome_generate.cpp): FASTA -> genomeDir, suffix array + SAindex built on the device
+    // (genomeFastaFiles below: the genome in genomeGenerate, references added to the index of --genomeDir in alignReads)
+    bool outSAMfilterKeepOnlyAdded = false, outSAMfilterKeepAllAdded = false;   // --outSAMfilter KeepOnlyAddedReferences | KeepAllAddedReferences (Parameters.cpp:740-761)
     bool runModeGenerate = false; std::vector<std::string> genomeFastaFiles; uint32_t genomeSAindexNbases = 14, genomeChrBinNbits = 18, genomeSAsparseD = 1;
     std::string bamRemoveDuplicatesType = "-";          // --bamRemoveDuplicatesType - | UniqueIdentical | UniqueIdenticalNotMulti (the tool mode; alignReads ignores it, as the reference does)
     uint32_t bamRemoveDuplicatesMate2basesN = 0;        // --bamRemoveDuplicatesMate2basesN
@@ -357,6 +364,13 @@ typedef int (*SjdbDeviceFn)(int device, const staramd_sjdb_args *a, staramd_sjdb
 void setSjdbDeviceFn(SjdbDeviceFn fn, int device);
 typedef int (*SjdbResidentFn)(void *user, const staramd_sjdb_args *a, staramd_sjdb_result *res);
 void setSjdbResidentFn(SjdbResidentFn fn, void *user);
+// --genomeFastaFiles at the mapping stage: the insertion of the added sequences' suffixes runs through fn (staramd_seq_insert of include/star_amd_index.h),
+// handed in by the front end that links the engine; there is no host restatement: without a function the run ends with SEQ_INSERT_MISSING
+typedef int (*SeqInsertFn)(int device, const staramd_seq_args *a, staramd_seq_result *res);
+void setSeqInsertFn(SeqInsertFn fn, int device);
+inline constexpr const char *SEQ_INSERT_MISSING = "EXITING because of fatal PARAMETERS error: --genomeFastaFiles at the mapping stage, but no sequence insertion function is installed (sah_set_seq_insert_fn)";
+std::string scanFastaFiles(const std::vector<std::string> &files, uint64_t binBases, std::vector<uint8_t> &G, std::vector<std::string> &chrName,
+                           std::vector<uint64_t> &chrStart, std::vector<uint64_t> &chrLength);      // genome_generate.cpp
 // --sjdbGTFfile at the mapping stage (gtf.cpp): junctions of the annotation appended to `loci` with priority 20
 std::string loadGTFjunctions(const RunParams &P, const GenomeIndex &gi, SjdbLoci &loci, const std::string &dirOut, std::string &log);
 

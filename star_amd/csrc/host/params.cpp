@@ -212,6 +212,11 @@ std::string RunParams::parse(int argc, char **argv) {
         else if (k == "outSAMprimaryFlag") { const std::string &s = one(k, v); if (s == "AllBestScore") outSAMprimaryAllBest = true; else if (s != "OneBestScore") err = "EXITING: unsupported --outSAMprimaryFlag " + s; }
         else if (k == "outSAMmapqUnique") outSAMmapqUnique = (int)I(k, v);
         else if (k == "outSAMattrIHstart") outSAMattrIHstart = (int)I(k, v);
+        else if (k == "outSAMfilter") {         // Parameters.cpp:740-754
+            if (v[0] == "KeepOnlyAddedReferences") outSAMfilterKeepOnlyAdded = true;
+            else if (v[0] == "KeepAllAddedReferences") outSAMfilterKeepAllAdded = true;
+            else if (v[0] != "None") err = "EXITING because of FATAL INPUT ERROR: unknown/unimplemented value for --outSAMfilter: " + v[0] + "\nSOLUTION: specify one of the allowed values: KeepOnlyAddedReferences or None\n";
+        }
         else if (k == "outSAMflagOR") outSAMflagOR = (uint32_t)U(k, v);
         else if (k == "outSAMflagAND") outSAMflagAND = (uint32_t)U(k, v);
         else if (k == "readNameSeparator") readNameSeparator = one(k, v);
@@ -416,6 +421,12 @@ std::string RunParams::parse(int argc, char **argv) {
     if (outSAMorderKeep && (outBAMunsorted || outBAMcoord || outSAMnone)) return "EXITING: fatal input ERROR: --outSAMorder=PairedKeepInputOrder is presently only compatible with SAM output, i.e. default --outSMAtype SAM\nSOLUTION: re-run STAR without --outSAMorder=PairedKeepInputOrder, or with --outSAMorder=PairedKeepInputOrder --outSMAtype SAM .\n";
     if (outSJnone && outFilterBySJout) return "EXITING because of FATAL input ERROR: --outFilterType BySJout requires --outSJtype Standard\nSOLUTION: --outFilterType Normal    OR   --outFilterType BySJout --outSJtype Standard\n";
     if (outSJnone && twopass) return "EXITING because of FATAL input ERROR: --twopassMode Basic needs the junctions of the 1st pass, i.e. --outSJtype Standard\n";
+    // Parameters.cpp:756-761
+    if ((outSAMfilterKeepOnlyAdded || outSAMfilterKeepAllAdded) && genomeFastaFiles.empty())
+        return "EXITING because of FATAL INPUT ERROR: --outSAMfilter KeepOnlyAddedReferences OR KeepAllAddedReferences options can only be used if references are added on-the-fly with --genomeFastaFiles\nSOLUTION: use default --outSAMfilter None, OR add references with --genomeFataFiles\n";
+    // the reference sizes the insertion only in its NoSharedMemory branch (Genome_genomeLoad.cpp:244-250) and would map against the old index in silence
+    if (!genomeFastaFiles.empty() && genomeLoadShared)
+        return "EXITING because of fatal PARAMETERS error: --genomeFastaFiles at the mapping stage is not compatible with genomeLoad shared memory options\nSOLUTION: re-run with --genomeLoad NoSharedMemory\n";
     if (twopass && genomeLoadShared) return "EXITING because of fatal PARAMETERS error: 2-pass method is not compatible with genomeLoad shared memory options\nSOLUTION: re-run STAR with --genomeLoad NoSharedMemory ; this is the only option compatible with --twopassMode Basic .\n";
     {   // read groups: one for all input files or one per file; the RG attribute comes with them (Parameters_readFilesInit.cpp:84-93, Parameters_samAttributes.cpp:201-206)
         size_t nFiles = readFilesIn.empty() ? 0 : (size_t)std::count(readFilesIn[0].begin(), readFilesIn[0].end(), ',') + 1;

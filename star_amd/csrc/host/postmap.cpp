@@ -1027,6 +1027,20 @@ std::string PostMap::processRange(const ReadBatch &b, const staramd_results &r, 
             recordSJ(P, trMult, nTr, sj);
             if (gc && nTr > 0) gc->addAlign(*genes, nTr, *trMult[0].t, trMult[0].ex);        // alignedAnnotation (ReadAlign_outputAlignments.cpp:298-308)
             if (quantBam) quantTranscriptome(P, gi, rc, *transcripts, trMult, nTr, b.mmMaxTotal[ir], *quantBam, *quantPatches);
+            // writeSAM's --outSAMfilter (:141-164), stated once for SAM, unsorted and sorted BAM: statistics, SJ.out.tab, gene counts and the transcriptome output
+            // above saw every alignment.  Where the reference returns early nothing below happens either: no record, no unmapped mate of a one-mate alignment,
+            // and mateMapped stays 00 with unmapType < 0, so the read reaches neither --outSAMunmapped Within nor --outReadsUnmapped, nor the unmapped count
+            if (P.outSAMfilterKeepOnlyAdded) {
+                bool old = false;
+                for (uint64_t it = 0; it < nTr; it++) if (trMult[it].t->Chr < gi.insertChrIndFirst) old = true;
+                if (old) continue;
+            } else if (P.outSAMfilterKeepAllAdded) {
+                uint64_t n1 = 0;
+                for (uint64_t it = 0; it < nTr; it++) if (trMult[it].t->Chr >= gi.insertChrIndFirst) { trMult[n1] = trMult[it]; trMult[n1].primary = false; ++n1; }
+                if (n1 == 0) continue;
+                trMult[0].primary = true;
+                nTr = n1;                    // NH / HI / MAPQ from the compacted count
+            }
             // writeSAM (:132-256): at most --outSAMmultNmax alignments are written (NH keeps the full count)
             const uint64_t nTrWrite = P.outSAMmultNmax < 0 ? nTr : std::min<uint64_t>(nTr, (uint64_t)P.outSAMmultNmax);
             const bool keepPairs = P.outSAMunmappedKeepPairs;

@@ -228,6 +228,10 @@ struct Runner {
         }
         error = gi.load(P.genomeDir);
         if (!error.empty()) return false;
+        if (!P.genomeFastaFiles.empty()) {                          // Genome_genomeLoad.cpp:374: references added to the loaded index
+            error = gi.insertSequences(P, insertLog);
+            if (!error.empty()) return false;
+        }
         if (P.sjdbInsertYes()) {
             // sjdbOverhang of the run (Genome_genomeLoad.cpp:113-125) and the run-time directories (Parameters.cpp:817-824,1019-1034)
             uint32_t gov = gi.view.sjdbOverhang;
@@ -674,6 +678,7 @@ uint64_t sah_batch_reads(void *h) { return ((Runner *)h)->P.gpuBatchReads; }
 // junction insertion (2-pass, --sjdbGTFfile / --sjdbFileChrStartEnd at the mapping stage, genomeGenerate with annotations) on the device:
 // fn = staramd_sjdb_insert of the engine library (include/star_amd_index.h); process-wide; NULL restores the host restatement
 void sah_set_sjdb_device_fn(int (*fn)(int, const staramd_sjdb_args *, staramd_sjdb_result *), int device) { staramd::setSjdbDeviceFn(fn, device); }
+void sah_set_seq_insert_fn(int (*fn)(int, const staramd_seq_args *, staramd_seq_result *), int device) { staramd::setSeqInsertFn(fn, device); }
 void sah_set_bgzf_device_fn(staramd::BgzfDeviceFn fn, void *user) { staramd::setBgzfDeviceFn(fn, user); }
 // the same on the arrays resident in the engine contexts (staramd_insert_junctions for every context): fn(user, args, result); the front end calls
 // sah_engines_ready once its contexts hold the index, and asks sah_index_in_engine after a phase change whether a re-upload is needed at all

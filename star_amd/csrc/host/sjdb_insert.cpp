@@ -548,7 +548,14 @@ std::string sjdbInsertJunctions(RunParams &P, GenomeIndex &gi, SjdbLoci &loci, b
     if (!err.empty()) return err;
     lap("prepare + build");
     if (P.sjdbInsertSaveAll) {                                             // sjdbInsertJunctions.cpp:70-98
-        if (gi.dir != outDir)
+        if (gi.seqInserted) {
+            // sequences were added (--genomeFastaFiles): the reference copies the OLD tables here as well (:72-78), which leaves a saved index whose
+            // chromosome tables do not describe its Genome; the tables of the new index are written instead (writeChrInfo, Genome_genomeGenerate.cpp:418-432)
+            std::ofstream chrN(outDir + "/chrName.txt"), chrS(outDir + "/chrStart.txt"), chrL(outDir + "/chrLength.txt"), chrNL(outDir + "/chrNameLength.txt");
+            const uint32_t nChr = gi.view.nChrReal;
+            for (uint32_t i = 0; i < nChr; i++) { chrN << gi.chrName[i] << "\n"; chrS << gi.chrStart[i] << "\n"; chrL << gi.chrLength[i] << "\n"; chrNL << gi.chrName[i] << "\t" << gi.chrLength[i] << "\n"; }
+            chrS << gi.chrStart[nChr] << "\n";
+        } else if (gi.dir != outDir)
             for (const char *f : {"chrName.txt", "chrStart.txt", "chrNameLength.txt", "chrLength.txt"}) copyFile(gi.dir + "/" + f, outDir + "/" + f);
         {
             std::ifstream in(gi.dir + "/genomeParameters.txt"); std::ofstream out(outDir + "/genomeParameters.txt");

@@ -5,6 +5,7 @@
 #include <string>
 #include "hip_backend.h"
 #include "sjdb_core.h"
+#include "seq_core.h"
 #include "../../../include/star_amd.h"
 #include "../../../include/star_amd_index.h"
 
@@ -73,5 +74,31 @@ extern "C" int staramd_sjdb_insert(int device, const staramd_sjdb_args *a, stara
     if (be.err != hipSuccess) { g_idxErr = std::string("staramd_sjdb_insert: ") + be.where + ": " + hipGetErrorString(be.err); return STARAMD_ERR_DEVICE; }
     if (rc == -2) { g_idxErr = "staramd_sjdb_insert: output buffers too small"; return STARAMD_ERR_RESULT_OVERFLOW; }
     if (rc == -3) { g_idxErr = "staramd_sjdb_insert: the first suffix has a non-ACGT base inside the SAindex prefix"; return STARAMD_ERR_ARG; }
+    return STARAMD_OK;
+}
+
+extern "C" int staramd_seq_insert(int device, const staramd_seq_args *a, staramd_seq_result *res) {
+    if (!a || !res || !a->G || !a->SA || !a->Gins || !a->SAout || !a->SAiOut) { g_idxErr = "staramd_seq_insert: null argument"; return STARAMD_ERR_ARG; }
+    if (a->nGins == 0 || a->nGenomeReal > a->nGenomeOld || a->gSAindexNbases < 1 || a->gSAindexNbases > 16 || a->nSAold == 0 || a->GstrandBit + 3 > 63) { g_idxErr = "staramd_seq_insert: bad parameters"; return STARAMD_ERR_ARG; }
+    int nDev = 0;
+    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev == 0) { g_idxErr = "no HIP device visible: sequence insertion runs on the GPU only (no CPU fallback in this library)"; return STARAMD_ERR_DEVICE; }
+    if (hipSetDevice(device) != hipSuccess) { g_idxErr = "hipSetDevice failed"; return STARAMD_ERR_DEVICE; }
+    HipBackend be;
+    if (hipStreamCreate(&be.s) != hipSuccess) { g_idxErr = "hipStreamCreate failed"; return STARAMD_ERR_DEVICE; }
+    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, be.s);
+    SeqParams P; P.nG = a->nGenomeReal; P.nG1 = a->nGins; P.nG2 = a->nGenomeOld - a->nGenomeReal; P.nSAold = a->nSAold; P.GstrandBit = a->GstrandBit; P.saIndexNbases = a->gSAindexNbases;
+    SeqHostArgs A{a->G, a->SA, a->nSAbyteOld, a->Gins, a->SAout, a->saOutCapacity, a->SAiOut, a->saiOutCapacity};
+    SeqDeviceResult R; u64 nb = 0, nbi = 0;
+    int rc = seqInsertHost(be, P, A, R, nb, nbi);
+    (void)hipEventRecord(e1, be.s); (void)hipStreamSynchronize(be.s);
+    float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
+    if (be.tmp) (void)hipFree(be.tmp);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipStreamDestroy(be.s);
+    memset(res, 0, sizeof(*res));
+    res->nInd = R.nInd; res->nSAnew = R.nSAnew; res->nSAbyteNew = nb; res->nSAibyte = nbi; res->nCapHits = R.nCapHits; res->doublingRounds = (uint32_t)R.rounds; res->msTotal = ms;
+    if (rc == -4) { g_idxErr = SEQ_STRANDBIT_ERROR; return STARAMD_ERR_ARG; }
+    if (be.err != hipSuccess) { g_idxErr = std::string("staramd_seq_insert: ") + be.where + ": " + hipGetErrorString(be.err); return STARAMD_ERR_DEVICE; }
+    if (rc == -2) { g_idxErr = "staramd_seq_insert: output buffers too small"; return STARAMD_ERR_RESULT_OVERFLOW; }
+    if (rc == -3) { g_idxErr = "staramd_seq_insert: the first suffix has a non-ACGT base inside the SAindex prefix"; return STARAMD_ERR_ARG; }
     return STARAMD_OK;
 }
